@@ -18,7 +18,10 @@ Rank 0 builds the world (scenes, vocabulary, local maps) and broadcasts it
 over RCCL (gf_dist_*, xGMI); each rank then tracks its own sequences (its own
 phases of the loops), weak scaling, no per-frame communication.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run does the set-up, the warm-up and
+the timed steps only; `--full` adds every other leg (rocprofv3 kernel table,
+CPU baseline, latency, budgets, local BA, config 3) and the detail file.
+`--dump-outputs DIR` writes the last timed step's results as .npy files.
 """
 from __future__ import annotations
 
@@ -567,7 +570,75 @@ def rocprof_kernel_table(args) -> tuple:
     return acc, len(queues), None
 
 
+# ------------------------------------------------------------- output dump
+DUMP_CAP = 60 * 1000 * 1000  # bytes of array data over all files (the files' headers stay under 64 MB with it)
+
+
+def dump_outputs(dirname: str, fes: list) -> dict:
+    """What the last step of the front ends handed back, as dirname/<name>.npy
+    (float32, counts and indices float64), streams in group order: every
+    stream's keypoint count, pose, velocity and tracking state; keypoints
+    (cv::KeyPoint fields in their order), map-point index per keypoint (-1:
+    none) and outlier flags of the streams in keypoint_streams.npy; the
+    descriptors (one byte per value) of the streams in descriptor_streams.npy.
+    The stream lists are every stream while DUMP_CAP allows, else a fixed
+    seeded sample (ascending). Slots past a stream's keypoint count are 0
+    (-1 in kp2mp). -> {name: shape}."""
+    def rd(name, sel=None):
+        a = np.concatenate([fe.read(name) for fe in fes])
+        return a if sel is None else a[sel]
+
+    nkp = rd("nkp")
+    B, cap = len(nkp), fes[0].cap
+    out = {"nkp": nkp.astype(np.float64), "Tcw": rd("Tcw").astype(np.float32),
+           "velocity": rd("velocity").astype(np.float32), "track": rd("track").astype(np.float64)}
+    left = DUMP_CAP - sum(a.nbytes for a in out.values()) - 16 * B
+    order = np.random.default_rng(0).permutation(B)
+    n_kp = int(min(B, (0.7 * left) // (cap * 36)))
+    n_de = int(min(B, (left - n_kp * cap * 36) // (cap * 128)))
+    s_kp, s_de = np.sort(order[:n_kp]), np.sort(order[:n_de])
+    live = np.arange(cap)[None, :] < nkp[s_kp, None]
+    kps = rd("kps", s_kp)
+    kp = np.stack([kps[f].astype(np.float32) for f in kps.dtype.names], -1)
+    kp[~live] = 0
+    out["keypoint_streams"] = s_kp.astype(np.float64)
+    out["keypoints"] = kp
+    out["kp2mp"] = np.where(live, rd("kp2mp", s_kp), -1).astype(np.float32)
+    out["outlier"] = np.where(live, rd("outlier", s_kp), 0).astype(np.float32)
+    de = rd("desc", s_de).astype(np.float32)
+    de[~(np.arange(cap)[None, :] < nkp[s_de, None])] = 0
+    out["descriptor_streams"] = s_de.astype(np.float64)
+    out["descriptors"] = de
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in out.items()}
+
+
 # ------------------------------------------------------------- main
+def _scene_worker(seed: int):
+    from gf_orb_slam_amd import scene
+
+    return scene.Scene(seed)
+
+
+def make_scenes(S: int, seed: int) -> list:
+    """The rooms scene.Workload(seed=seed) renders for itself (Scene(seed * 1000
+    + s), host numpy only), made by one worker process per CPU of the job's
+    share: most of the set-up time when made one after another. The workers
+    are fresh interpreters and never touch the GPU. Under a profiler (the
+    rocprofv3 child of --full) they are made in this process: the profiler's
+    environment would follow the workers."""
+    import multiprocessing as mp_
+
+    seeds = [seed * 1000 + s for s in range(S)]
+    w = min(len(cpu_share()), S)
+    if w < 2 or _under_profiler():
+        return [_scene_worker(s) for s in seeds]
+    with mp_.get_context("spawn").Pool(w) as pool:
+        return pool.map(_scene_worker, seeds)
+
+
 def build_world(cam: str, B: int, S: int, period: int, nfeat: int, nmap: int, device: int, stale: float,
                 refmap: bool, n_kf: int):
     """Rank 0: the scenes of the loops and each scene's map (keyframes
@@ -577,7 +648,8 @@ def build_world(cam: str, B: int, S: int, period: int, nfeat: int, nmap: int, de
     keyframe-built local map."""
     from gf_orb_slam_amd import ORBextractor, scene
 
-    W0 = scene.Workload(cam, B, n_scenes=S, period=period, seed=0, stale_desc=stale)
+    W0 = scene.Workload(cam, B, n_scenes=S, period=period, seed=0, stale_desc=stale,
+                        scenes=make_scenes(min(S, B), 0))
     ex = ORBextractor(nfeat, 1.2, 8, 1, 20)
     if refmap:
         gm = W0.build_global_maps(lambda im: ex(im), nmap, n_kf=n_kf, device=f"cuda:{device}")
@@ -599,6 +671,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the rocprofv3 kernel table, the isolated, "
+                         "budgets-on, stage-log, single-sequence, host-frames, local-BA and config-3 legs, the CPU "
+                         "baseline, and the detail file. Without it the run sets up, warms up, times --steps steps "
+                         "and prints the line; the options of those legs then have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step handed back (every sequence's "
+                         "keypoints, pose, matches, outlier flags, velocity, tracking state; the descriptors of a "
+                         "fixed seeded sample of sequences) as DIR/<name>.npy, float32 / float64, <= 64 MB in all")
     ap.add_argument("--batch", type=int, default=1024, help="independent sequences per GPU")
     ap.add_argument("--groups", type=int, default=4,
                     help="stream groups per GPU, each a front end on its own HIP stream (their kernels overlap; 4 x 256 measured best in r03: 95.9k vs 89.5k frames/s for 2 x 512)")
@@ -675,6 +756,10 @@ def main():
                          "launches); default: every stream relocalises against its scene's keyframes")
     args = ap.parse_args()
 
+    if not args.full:  # the plain run: set-up, warm-up, the timed steps, the line
+        args.kernel_times, args.no_cpu_baseline = "events", True
+        args.lba_batch = args.single_stream_steps = args.isolated_steps = args.budget_steps = 0
+        args.pcie_steps = args.config3_steps = args.time_log_steps = 0
     if args.hw_queues > 0:  # before anything initialises the HIP runtime
         os.environ["GPU_MAX_HW_QUEUES"] = str(min(args.hw_queues, 32))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -870,6 +955,9 @@ def main():
     final = {k: np.concatenate([s[k] for s in stats]) for k in STATS}
     thist = np.concatenate([fe.read("hist") for fe in fes]).astype(np.int64)  # [B][8] over the timed steps
     trk = np.concatenate([fe.read("track") for fe in fes])  # GF_FE_TRACK after the timed steps
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, fes)
     if args.no_prof_timed:  # the kernel table from a profiled pass of the same steps
         for fe in fes:
             fe.prof_enable(True)
@@ -1317,7 +1405,11 @@ def main():
             "aggregate_speedup_one_gpu": [round(fps / world / 90.9, 1), round(fps / world / 62.5, 1)],
             "note": "GPU figures over the reference's published per-frame latency range (read off its plot, "
                     "hardware not stated); `value` above is this repo's scalar C++ port timed here"}
-    if rank == 0:
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if rank == 0 and not args.full and not args.detail_out:  # the plain run writes no record unless asked to
+        print(compact_line(out, None), flush=True)
+    elif rank == 0:
         detail = args.detail_out or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
         try:
             os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)

@@ -11,7 +11,7 @@ if [ -n "$TESTS" ]; then
   timeout -k 10 600 python -u -m pytest $TESTS -m gpu -x -q --timeout 200 --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 10; }
   echo "tests: $(tail -1 $O/pytest.log)"
 fi
-ARGS="--no-cpu-baseline --lba-batch 0 --config3-steps 0 --budget-steps 0 --pcie-steps 0 --isolated-steps 0 --time-log-steps 0 ${BENCH_ARGS}"
+ARGS="--full --no-cpu-baseline --lba-batch 0 --config3-steps 0 --budget-steps 0 --pcie-steps 0 --isolated-steps 0 --time-log-steps 0 ${BENCH_ARGS}"
 for v in ${VARS//,/ }; do
   case $v in product*) lib="";; base*) lib=$R/gf_orb_slam_amd/diag/libgfslam_base.so;; *) lib=$R/gf_orb_slam_amd/diag/libgfslam_${v}.so;; esac
   GF_LIB=$lib timeout -k 10 400 python bench.py $ARGS --detail-out $R/$O/$v.json --kernel-trace-dir $R/$O/kt_$v > $O/$v.line 2> $O/$v.err || { tail -20 $O/$v.err; exit 11; }

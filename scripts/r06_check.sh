@@ -18,7 +18,7 @@ if [ "$2" != "skip-tests" ]; then
   fi
 fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 13
-timeout -k 10 600 python bench.py ${BENCH_ARGS} --detail-out $R/$O/bench_detail.json --kernel-trace-dir $R/$O/ktrace --time-log $R/$O/time_log.txt > $O/bench.json 2> $O/bench.err || exit 11
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS} --detail-out $R/$O/bench_detail.json --kernel-trace-dir $R/$O/ktrace --time-log $R/$O/time_log.txt > $O/bench.json 2> $O/bench.err || exit 11
 rm -f $O/ktrace/*kernel_trace.csv
 head -c 600 $O/bench.json
 exit 0

@@ -18,7 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_two_ranks_host_transport(tmp_path):
     B, steps = 64, 3
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--dist-transport", "host", "--batch", str(B), "--groups", "2",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--dist-transport", "host", "--batch", str(B),
+           "--groups", "2",
            "--steps", str(steps), "--warmup", "1", "--scenes", "4", "--keyframes", "8", "--no-cpu-baseline",
            "--lba-batch", "0", "--single-stream-steps", "0", "--isolated-steps", "0", "--budget-steps", "0",
            "--pcie-steps", "0", "--config3-steps", "0", "--kernel-times", "events", "--time-log-steps", "4",
