@@ -9,10 +9,13 @@
 //   k_blur_fast              one 64x64 tile per workgroup: 7x7 sigma-2
 //                            Gaussian of every level (:842) and, from the same
 //                            LDS tile, the FAST-9 score map of the level
-//   k_fast_cells             one workgroup per (frame, grid cell): corners of
-//                            the cell window from the score map, in-cell NMS,
-//                            threshold fallback 20 -> 7, row-major compaction
-//                            (ComputeKeyPoints :575-689)
+//   k_nms_tiles              one wave per 256 x 32 strip of a level: 3x3 NMS of
+//                            the score map inside the cells' windows, to a
+//                            survivor bit plane
+//   k_cell_lists             one wave per (frame, grid cell): the window's
+//                            survivors in row-major order (ComputeKeyPoints
+//                            :575-689); a cell with at most 3 is queued
+//   k_cell_retry             the queued cells: threshold fallback 20 -> 7
 //   k_select                 one workgroup per (frame, level): quota
 //                            redistribution (:695-721) + retainBest per cell
 //                            and per level (:734-752)
@@ -68,7 +71,7 @@ struct CellInfo {
     int level, x0, y0, w, h, valid;
     long long cap_off;
     int cap;
-    int band;  // 0: the window fits k_fast_cells' LDS; else rows per band of k_fast_cells_band
+    int band;  // 0: the window fits k_cell_retry's LDS; else rows per band of k_fast_cells_band
 };
 
 struct Planes {
@@ -456,7 +459,7 @@ __device__ int block_scan_256(int v, int* tmp, int& total) {
 //     test, else 0 (and 0 within 3 px of the level border). The cells run
 //     their fast_th pass, NMS included, from this map; the rare cell that
 //     retries at minThFAST (:623-628) recomputes its window from the level
-//     (k_fast_cells).
+//     (k_cell_retry).
 // LDS column j of the source tile holds x = X0 - 4 + j, so the tile's rows are
 // whole dwords, loaded as aligned global dwords realigned with v_alignbyte
 // (two loads per dword, all in flight together); only the dwords at the
@@ -749,21 +752,20 @@ __global__ __launch_bounds__(256) void k_blur_fast(Planes P, LevelGeom g, uint8_
     }
 }
 
-// -------------------------------------------------------------- k_fast_cells
-// One workgroup per (grid cell, frame). The cell's detection window (the ROI
-// minus its 3-px FAST margin, :621) of the score map goes to LDS; corners at
-// fast_th survive strict 3x3 non-maximum suppression inside the window
-// (neighbours outside it or not corners count 0, as in FAST's row buffers)
-// and are listed in row-major order. When at most 3 survive (:623-628) the
-// window's map is recomputed at min_th from the unblurred level (the ROI's
-// pixels, staged in LDS), suppressed again and the list rewritten.
-// NMS: wave w walks rows [w dh/4, (w+1) dh/4) of each 64-column strip, lane =
-// column, keeping the three rows it compares in registers (three LDS reads a
-// pixel); survivors set their bit in an LDS bit array (bit = row-major pixel
-// index). Listing: a workgroup scan over the popcounts of the bit words.
-// (Cell windows are at most ~40 px wide, so one strip.)
+// -------------------------------------------------------------- the cells' corners
+// Per (grid cell, frame): in the cell's detection window (the ROI minus its
+// 3-px FAST margin, :621) of the score map, corners at fast_th survive strict
+// 3x3 non-maximum suppression inside the window (neighbours outside it or not
+// corners count 0, as in FAST's row buffers) and are listed in row-major
+// order. When at most 3 survive (:623-628) the window's map is recomputed at
+// min_th from the unblurred level, suppressed again and the list rewritten.
+// k_nms_tiles suppresses whole levels at fast_th, k_cell_lists lists a cell,
+// k_cell_retry runs its retry; k_fast_cells_band does all of it for a cell whose
+// window is too large for k_cell_retry's LDS.
 
-// sc: the window rows as loaded (row y at byte y * pitch + rsh[y]). Every LDS
+// cell_nms_bits (k_fast_cells_band): lane = column of a 64-column strip, the
+// three rows it compares in registers; survivors set their bit in an LDS bit
+// array. sc: the window rows as loaded (row y at byte y * pitch + rsh[y]). Every LDS
 // read is unconditional (addresses clamped into the window, out-of-window
 // values replaced by 0 afterwards) and each row's base offset is read one
 // step before the row itself, so a row step issues its reads together and
@@ -839,13 +841,6 @@ __device__ __forceinline__ int cell_nms_bits(const uint8_t* sc, const uint8_t* r
     return cnt;  // this wave's survivors
 }
 
-// FC_THREADS: workgroup size (64: one wave per cell, no workgroup barrier)
-#ifndef FC_THREADS
-#define FC_THREADS 256
-#endif
-constexpr int FC_NT = FC_THREADS, FC_NW = FC_THREADS / 64;
-static_assert(FC_NT == 64 || FC_NT == 256 || FC_NT == 512, "k_fast_cells: 1, 4 or 8 waves");
-
 // Exclusive scan of one int per thread across an NW-wave workgroup.
 template <int NW>
 __device__ int block_scan_nw(int v, int* tmp, int& total) {
@@ -864,20 +859,17 @@ __device__ int block_scan_nw(int v, int* tmp, int& total) {
     __syncthreads();
     return base + x;
 }
-__device__ __forceinline__ void fc_sync() {
-    if constexpr (FC_NT == 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// k_fast_cells' LDS: the window's score rows realigned to column 0, with a
-// zero row above and below and a zero dword either side (the 3x3 NMS reads
-// its out-of-window neighbours as 0, as FAST's row buffers hold 0 there);
-// survivor bits per window row in whole 32-bit words; the retry's ROI.
+// The LDS of one cell's minimum-threshold retry (k_cell_retry): the window's
+// score rows from column 0, with a zero row above and below and a zero dword
+// either side (the 3x3 NMS reads its out-of-window neighbours as 0, as
+// FAST's row buffers hold 0 there); survivor bits per window row in whole
+// 32-bit words; the ROI.
 struct FcLayout {
     int nq, ndw, pitch, wpr, nwords;
     size_t sc_bytes, bits_bytes, total;
@@ -895,7 +887,7 @@ __host__ __device__ inline FcLayout fc_layout(int dw, int dh, int w, int h) {
     return L;
 }
 
-// 3x3 strict NMS over k_fast_cells' realigned window, four columns per lane
+// 3x3 strict NMS over the retry's window in LDS, four columns per lane
 // (lane L: columns 4L .. 4L + 3) on packed 16-bit lanes: per row the dwords
 // L - 1, L, L + 1 give the even columns E = (4L, 4L + 2), the odd O = (4L + 1,
 // 4L + 3) and their left / right neighbour pairs EL = (4L - 1, 4L + 1), OR =
@@ -904,6 +896,7 @@ __host__ __device__ inline FcLayout fc_layout(int dw, int dh, int w, int h) {
 // order and sends the others to 0, so "m > every counted neighbour and m
 // counted" is m' > the neighbours' max m'. Wave w takes window rows [w dh / NW,
 // (w + 1) dh / NW); one pass covers 256 columns. Returns the wave's survivors.
+// (k_nms_tiles does the same arithmetic on the map.)
 template <int NWV>
 __device__ __forceinline__ int cell_nms4(const uint32_t* sc32, const FcLayout& Ly, uint32_t* bits, int dh, int th) {
     typedef unsigned short u2 __attribute__((ext_vector_type(2)));
@@ -959,130 +952,369 @@ __device__ __forceinline__ int cell_nms4(const uint32_t* sc32, const FcLayout& L
     return gfd::warp_sum(cnt);
 }
 
+// -------------------------------------------------------------- k_nms_tiles
+// 3x3 strict NMS at fast_th over whole levels. The detection windows of a
+// level's cells tile it without overlap (a window is its cell's ROI minus the
+// 3-px margin, the next cell starts one cell width on), and the grid is a
+// product: a pixel's window is (the cell column of x, the cell row of y). So
+// "suppress inside the window, neighbours outside it count 0" needs, on full
+// rows of the map, only masks by x and flags by y, both made on the host from
+// the CellInfo table (nms_plan):
+//   * the column table, one entry per dword column q (columns 4q .. 4q + 3):
+//     bit i: column 4q + i lies in a window; bit 4 + i / 8 + i: its left /
+//     right neighbour lies in the same window;
+//   * per task, bit r of in / up / dn: row y0 + r lies in a window row / the
+//     row above / below lies in the same one.
+// One wave per task: 64 dword columns x up to NMS_ROWS rows, lane = dword
+// column, the three rows it compares in registers (cell_nms4's arithmetic on
+// packed 16-bit lanes, there on a window in LDS). Rows are loaded as aligned
+// dwords of the pitched map, several rows in flight; the left / right
+// neighbour dwords come from the adjacent lanes (DPP wave shifts), those of
+// lanes 0 and 63 from a second load. A neighbour counts when it lies in the
+// centre's window: the four neighbour pairs of a row are masked by the column
+// masks, the rows above and below by the row flags (a window row's first and
+// last row only; the rows between take a path without them), and a centre
+// outside every window is dropped from the result.
+// Output: the survivor plane, one bit per pixel, row-major words (bit x & 31
+// of word x >> 5) at the score map's offsets / 8; eight lanes' nibbles are
+// gathered into a word with three row-shift ORs. Rows outside every window
+// row are never written (the plane is zeroed once).
+#define NMS_ROWS 32
+#define NMS_PF 4  // rows per load batch (two batches in flight)
+struct NmsTask {
+    int level, q0, y0, nrows;  // dword columns q0 .. q0 + 63 of rows y0 .. y0 + nrows - 1
+    uint32_t in, up, dn;
+    int xoff;  // the level's first entry of the column table
+};
+
+__global__ __launch_bounds__(256) void k_nms_tiles(LevelGeom g, const uint8_t* __restrict__ score,
+                                                   const NmsTask* __restrict__ tasks, int ntasks,
+                                                   const uint32_t* __restrict__ xtab, uint32_t* __restrict__ surv,
+                                                   int th, int* __restrict__ retry) {
+    gfd::ext_prio();
+    typedef unsigned short u2 __attribute__((ext_vector_type(2)));
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) retry[0] = 0;  // k_cell_lists' retry queue
+    int blk, f;
+    gfd::xcd_block(blk, f);
+    const int lane = threadIdx.x & 63;
+    const int t = __builtin_amdgcn_readfirstlane(4 * blk + (int)(threadIdx.x >> 6));
+    if (t >= ntasks) return;
+    const NmsTask tk = tasks[t];
+    const int l = tk.level, pw = g.pw[l], nq = pw >> 2, h = g.h[l];
+    const int q = tk.q0 + lane;
+    const bool okq = q < nq;
+    const int qc = min(q, nq - 1);
+    // lane 0's left and lane 63's right neighbour dword (the other lanes re-read their own)
+    const int qh = lane == 0 ? q - 1 : q + 1;
+    const int qhc = ((lane == 0 || lane == 63) && qh >= 0 && qh < nq) ? qh : qc;
+    const uint32_t xm = okq ? gfd::ldg(xtab + tk.xoff + qc) : 0u;
+    auto pair16 = [](uint32_t b, int i, int j) {
+        return ((b >> i) & 1u ? 0xffffu : 0u) | ((b >> j) & 1u ? 0xffff0000u : 0u);
+    };
+    // columns (4q, 4q + 2) = E, (4q + 1, 4q + 3) = O: their left / right neighbours in the same window.
+    // (A neighbour in no window is in no column's window, so these also drop the entries outside every
+    // window, the halo dwords' included; a column outside every window is dropped from the result, inx.)
+    const uint32_t mEL = pair16(xm, 4, 6), mOL = pair16(xm, 5, 7), mER = pair16(xm, 8, 10), mOR = pair16(xm, 9, 11);
+    const uint32_t inx = xm & 15u;
+    const unsigned short t1 = (unsigned short)max(th, 1);
+    const u2 T = {t1, t1}, ONE = {1, 1};
+    auto U = [](uint32_t v) { return __builtin_bit_cast(u2, v); };
+    auto V = [](u2 v) { return __builtin_bit_cast(uint32_t, v); };
+    // rows through a buffer descriptor of the level's map: the row offset is scalar, the lane's constant
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(score + (long long)f * g.bslab + g.boff[l]), 0, pw * h, 0x00020000);
+    const int voff = 4 * qc, hoff = 4 * qhc;
+    struct Raw {
+        uint32_t b, hb;
+    };
+    auto load = [&](int y) -> Raw {  // a row past the level reads its nearest row (masked by the row flags)
+        const int ro = min(max(y, 0), h - 1) * pw;
+        return Raw{(uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, voff, ro, 0),
+                   (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, hoff, ro, 0)};
+    };
+    // a row's m' = sat(m - t1): e, o the lane's columns; hE / hO the max of an E / O column's left and right
+    // neighbour in its window, vE / vO that of the three columns around it
+    struct Row {
+        u2 e, o, hE, hO, vE, vO;
+    };
+    auto make = [&](Raw r) -> Row {
+        const uint32_t b = r.b;
+        const uint32_t a = (uint32_t)__builtin_amdgcn_update_dpp((int)r.hb, (int)b, 0x138, 0xf, 0xf, false);  // wave_shr:1
+        const uint32_t c = (uint32_t)__builtin_amdgcn_update_dpp((int)r.hb, (int)b, 0x130, 0xf, 0xf, false);  // wave_shl:1
+        Row x;
+        x.e = __builtin_elementwise_sub_sat(U(__builtin_amdgcn_perm(0u, b, 0x0c020c00u)), T);
+        x.o = __builtin_elementwise_sub_sat(U(__builtin_amdgcn_perm(0u, b, 0x0c030c01u)), T);
+        const u2 el = __builtin_elementwise_sub_sat(U(__builtin_amdgcn_perm(a, b, 0x0c010c07u)), T);
+        const u2 orr = __builtin_elementwise_sub_sat(U(__builtin_amdgcn_perm(c, b, 0x0c040c02u)), T);
+        x.hE = __builtin_elementwise_max(U(V(el) & mEL), U(V(x.o) & mER));
+        x.hO = __builtin_elementwise_max(U(V(x.e) & mOL), U(V(orr) & mOR));
+        x.vE = __builtin_elementwise_max(x.hE, x.e);
+        x.vO = __builtin_elementwise_max(x.hO, x.o);
+        return x;
+    };
+    const int spw = pw >> 5;  // words per row of the survivor plane
+    uint32_t* srow = surv + (long long)f * (g.bslab >> 5) + (g.boff[l] >> 5) + (long long)tk.y0 * spw + (q >> 3);
+    const bool st = okq && (lane & 7) == 7;
+    const int sh = 4 * (lane & 7);
+    // the survivors of row y0 + r (its rows above, at and below: u, c, d) to the plane
+    auto put = [&](int r, u2 mxE, u2 mxO, const Row& c) {
+        // bit i of the nibble: column 4q + i (E: bits 0 and 2, O: bits 1 and 3, the second column of each
+        // in the high half)
+        const uint32_t k = V(__builtin_elementwise_min(__builtin_elementwise_sub_sat(c.e, mxE), ONE)) |
+                           (V(__builtin_elementwise_min(__builtin_elementwise_sub_sat(c.o, mxO), ONE)) << 1);
+        uint32_t v = ((k | (k >> 14)) & inx) << sh;
+        v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
+        v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
+        v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
+        if (st) srow[(long long)r * spw] = v;  // lanes 8j + 7: the word of lanes 8j .. 8j + 7
+    };
+    auto step = [&](int r, const Row& u, const Row& c, const Row& d) {
+        const bool up = (tk.up >> r) & 1u, dn = (tk.dn >> r) & 1u;
+        if (up && dn) {  // inside a window row (most rows)
+            put(r, __builtin_elementwise_max(c.hE, __builtin_elementwise_max(u.vE, d.vE)),
+                __builtin_elementwise_max(c.hO, __builtin_elementwise_max(u.vO, d.vO)), c);
+        } else if ((tk.in >> r) & 1u) {  // its first or last row
+            const uint32_t su = up ? ~0u : 0u, sd = dn ? ~0u : 0u;
+            put(r, __builtin_elementwise_max(c.hE, __builtin_elementwise_max(U(V(u.vE) & su), U(V(d.vE) & sd))),
+                __builtin_elementwise_max(c.hO, __builtin_elementwise_max(U(V(u.vO) & su), U(V(d.vO) & sd))), c);
+        } else if (st) {
+            srow[(long long)r * spw] = 0u;
+        }
+    };
+    Row u = make(load(tk.y0 - 1)), c = make(load(tk.y0));
+    Raw cur[NMS_PF], nxt[NMS_PF];
+#pragma unroll
+    for (int k = 0; k < NMS_PF; k++) cur[k] = load(tk.y0 + 1 + k);
+    for (int r0 = 0; r0 < tk.nrows; r0 += NMS_PF) {
+#pragma unroll
+        for (int k = 0; k < NMS_PF; k++) nxt[k] = load(tk.y0 + 1 + r0 + NMS_PF + k);
+#pragma unroll
+        for (int k = 0; k < NMS_PF; k++) {
+            if (r0 + k < tk.nrows) {
+                const Row d = make(cur[k]);
+                step(r0 + k, u, c, d);
+                u = c;
+                c = d;
+            }
+            cur[k] = nxt[k];
+        }
+    }
+}
+
+// -------------------------------------------------------------- k_cell_lists
+// One wave per (grid cell, frame), four cells per workgroup, no LDS and no
+// workgroup barrier. A cell's survivors are the bits of its window in the
+// survivor plane (k_nms_tiles), read as words of 32 window columns (word i =
+// window row i / wpr, columns 32 (i % wpr) ..: two plane words funnel-shifted
+// by the window's bit offset); the survivors are listed in row-major order
+// (FAST's order) by wave scans over the words' popcounts, the score read from
+// the map. The kernel is a chain of dependent loads (cell, words, scores)
+// with little work between them, so a wave takes the first CL_NW x 64 words
+// of its window through each link together: all the words, the scans, every
+// word's first CL_NS scores, then the entries.
+// A cell with at most 3 survivors (ORBextractor.cc:623-628) is not listed
+// here: it is queued for k_cell_retry (retry[0]: the queue's length, zeroed by
+// k_nms_tiles; retry[1 + i]: f * ncells + cid).
+#define CL_NW 5
+#define CL_NS 2
+struct CellWin {
+    int dw, dh, l, lw, spw, X0, Y0, wpr, nwords;
+    float rwpr;
+    const uint32_t* SV;  // the survivor plane at the window's first row
+    const uint8_t* SC;   // the score map at the window's first pixel
+};
+__device__ __forceinline__ CellWin cell_win(const CellInfo& ci, const LevelGeom& g, const uint8_t* score,
+                                            const uint32_t* surv, int f) {
+    CellWin c;
+    c.dw = ci.w - 6;
+    c.dh = ci.h - 6;
+    c.l = ci.level;
+    c.lw = g.pw[c.l];
+    c.spw = c.lw >> 5;
+    c.X0 = ci.x0 + 3;
+    c.Y0 = ci.y0 + 3;
+    c.wpr = (c.dw + 31) >> 5;
+    c.nwords = c.dh * c.wpr;
+    c.rwpr = 1.0f / (float)c.wpr;
+    c.SV = surv + (long long)f * (g.bslab >> 5) + (g.boff[c.l] >> 5) + (long long)c.Y0 * c.spw;
+    c.SC = score + (long long)f * g.bslab + g.boff[c.l] + (long long)c.Y0 * c.lw + c.X0;
+    return c;
+}
+// Word i of the window (0 past its last word; the loads are unconditional, at the last word's address).
+__device__ __forceinline__ uint32_t cell_word(const CellWin& c, int i) {
+    const int ic = min(i, c.nwords - 1);
+    const int y = pyr_div(ic, c.rwpr), k = ic - y * c.wpr;
+    const int xs = c.X0 + 32 * k, wi = xs >> 5, n = c.dw - 32 * k;
+    const uint32_t* p = c.SV + (long long)y * c.spw;
+    // (the row's last word: its window bits end inside it, the second word is not needed)
+    const uint32_t lo = gfd::ldg(p + wi), hi = gfd::ldg(p + min(wi + 1, c.spw - 1));
+    const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, (uint32_t)(xs & 31));
+    return i < c.nwords ? (n >= 32 ? w : w & ((1u << n) - 1u)) : 0u;
+}
+
 template <typename E>
-__global__ __launch_bounds__(FC_NT) void k_fast_cells(Planes P, LevelGeom g, const uint8_t* __restrict__ score,
+__global__ __launch_bounds__(256) void k_cell_lists(Planes P, LevelGeom g, const uint8_t* __restrict__ score,
+                                                    const uint32_t* __restrict__ surv,
                                                     const CellInfo* __restrict__ cells, E* __restrict__ lists,
-                                                    long long list_stride, int* __restrict__ counts, int fast_th,
+                                                    long long list_stride, int* __restrict__ counts,
+                                                    int* __restrict__ retry) {
+    gfd::ext_prio();
+    int blk, f;
+    gfd::xcd_block(blk, f);
+    const int lane = threadIdx.x & 63;
+    const int cid = __builtin_amdgcn_readfirstlane(4 * blk + (int)(threadIdx.x >> 6));
+    if (cid >= g.ncells) return;
+    const CellInfo ci = cells[cid];
+    if (ci.band) return;  // a window past k_cell_retry's LDS: k_fast_cells_band
+    if (!ci.valid || ci.w - 6 <= 0 || ci.h - 6 <= 0) {  // degenerate ROI: FAST finds nothing
+        if (lane == 0) counts[(long long)f * g.ncells + cid] = 0;
+        return;
+    }
+    const CellWin c = cell_win(ci, g, score, surv, f);
+    uint32_t w[CL_NW];
+#pragma unroll
+    for (int j = 0; j < CL_NW; j++) w[j] = cell_word(c, 64 * j + lane);
+    int off[CL_NW], tot[CL_NW], total = 0;
+#pragma unroll
+    for (int j = 0; j < CL_NW; j++) {
+        off[j] = wave_scan_excl(__popc(w[j]), tot[j]);
+        total += tot[j];
+    }
+    int rest = 0;  // (a window of more than CL_NW x 64 words)
+    for (int i0 = 64 * CL_NW; i0 < c.nwords; i0 += 64) rest += __popc(cell_word(c, i0 + lane));
+    if (c.nwords > 64 * CL_NW) total += gfd::warp_sum(rest);
+    if (total <= 3) {  // ORBextractor.cc:623-628: retry with the minimum threshold
+        if (lane == 0) retry[1 + atomicAdd(retry, 1)] = f * g.ncells + cid;
+        return;
+    }
+    E* out = lists + (long long)f * list_stride + ci.cap_off;
+    // every word's first CL_NS survivors: positions and scores (a word without one
+    // reads the window's first pixel), all loads in flight together
+    int sx[CL_NW][CL_NS], sy[CL_NW], sS[CL_NW][CL_NS];
+#pragma unroll
+    for (int j = 0; j < CL_NW; j++) {
+        const int i = 64 * j + lane;
+        const int y = pyr_div(i, c.rwpr), xw = 32 * (i - y * c.wpr);
+        sy[j] = y;
+        uint32_t word = w[j];
+#pragma unroll
+        for (int s = 0; s < CL_NS; s++) {
+            const bool has = word != 0u;
+            const int x = xw + __ffs(word) - 1;
+            word &= word - 1;
+            sx[j][s] = has ? x : -1;
+            sS[j][s] = gfd::ldg(c.SC + (has ? (long long)y * c.lw + x : 0ll));
+        }
+        w[j] = word;  // the word's survivors past its first CL_NS
+    }
+    int base = 0;
+#pragma unroll
+    for (int j = 0; j < CL_NW; j++) {  // words in row-major order: the survivors in FAST's order
+        int o = base + off[j];
+#pragma unroll
+        for (int s = 0; s < CL_NS; s++)
+            if (sx[j][s] >= 0) out[o++] = cell_entry<E>(sS[j][s] - 1, c.X0 + sx[j][s], c.Y0 + sy[j], P, g, f, c.l);
+        uint32_t word = w[j];
+        while (word) {
+            const int x = 32 * (64 * j + lane - sy[j] * c.wpr) + __ffs(word) - 1;
+            word &= word - 1;
+            const int S = gfd::ldg(c.SC + (long long)sy[j] * c.lw + x) - 1;
+            out[o++] = cell_entry<E>(S, c.X0 + x, c.Y0 + sy[j], P, g, f, c.l);
+        }
+        base += tot[j];
+    }
+    for (int i0 = 64 * CL_NW; i0 < c.nwords; i0 += 64) {
+        const int i = i0 + lane;
+        uint32_t word = cell_word(c, i);
+        int t;
+        int o = base + wave_scan_excl(__popc(word), t);
+        const int y = pyr_div(i, c.rwpr), xw = 32 * (i - y * c.wpr);
+        while (word) {
+            const int x = xw + __ffs(word) - 1;
+            word &= word - 1;
+            const int S = gfd::ldg(c.SC + (long long)y * c.lw + x) - 1;
+            out[o++] = cell_entry<E>(S, c.X0 + x, c.Y0 + y, P, g, f, c.l);
+        }
+        base += t;
+    }
+    if (lane == 0) counts[(long long)f * g.ncells + cid] = total;
+}
+
+// -------------------------------------------------------------- k_cell_retry
+// The minimum-threshold retry of the queued cells (ORBextractor.cc:623-628),
+// 256-thread workgroups taking queue entries in turn: the cell's ROI (window
+// + 3-px ring margin) of the unblurred level goes to LDS, the window's map is
+// recomputed at min_th, suppressed (cell_nms4: survivor bits per window row
+// in whole words, in LDS) and listed by a workgroup scan over the words.
+template <typename E>
+__global__ __launch_bounds__(256) void k_cell_retry(Planes P, LevelGeom g, const CellInfo* __restrict__ cells,
+                                                    E* __restrict__ lists, long long list_stride,
+                                                    int* __restrict__ counts, const int* __restrict__ retry,
                                                     int min_th) {
     gfd::ext_prio();
     extern __shared__ __align__(16) uint8_t smem[];
-    __shared__ int s_cnt[2][FC_NW];
-    __shared__ int scan_tmp[FC_NW];
-    int cid, f;
-    gfd::xcd_block(cid, f);
+    __shared__ int s_cnt[4];
+    __shared__ int scan_tmp[4];
     const int tid = threadIdx.x;
-    const CellInfo ci = cells[cid];
-    if (ci.band) return;  // a window past this kernel's LDS: k_fast_cells_band
-    const int dw = ci.w - 6, dh = ci.h - 6;
-    if (!ci.valid || dw <= 0 || dh <= 0) {  // degenerate ROI: FAST finds nothing
-        if (tid == 0) counts[(long long)f * g.ncells + cid] = 0;
-        return;
-    }
-    const FcLayout Ly = fc_layout(dw, dh, ci.w, ci.h);
-    uint8_t* sc = smem;  // window row y, column x at (y + 1) * pitch + 4 + x
-    uint32_t* sc32 = reinterpret_cast<uint32_t*>(smem);
-    uint32_t* bits = reinterpret_cast<uint32_t*>(smem + Ly.sc_bytes);  // window row y: words y * wpr ..
-    const int l = ci.level, lw = g.pw[l];
-    const uint8_t* SC = score + (long long)f * g.bslab + g.boff[l] + (long long)(ci.y0 + 3) * lw + ci.x0 + 3;
-    {  // the window realigned: every row of the pitched map has SC's byte shift.
-        // Thread t owns LDS dword column j = t % ndw of rows t / ndw + k rstep,
-        // so a row's address is one step from the last (no index split per load)
-        const uint32_t sh = (uint32_t)((uintptr_t)SC & 3u);
-        const uint32_t* SCa = reinterpret_cast<const uint32_t*>((uintptr_t)SC & ~(uintptr_t)3);
-        const int lw4 = lw >> 2, nrows = dh + 2;
-        const int ndw = Ly.ndw, rstep = max(FC_NT / ndw, 1);
-        const int j = tid % ndw, r0 = tid / ndw;
-        const bool jdata = j >= 1 && j <= Ly.nq;
-        uint32_t bmask = ~0u;  // the window's bytes of this dword column
-        if (jdata && dw - 4 * (j - 1) < 4) bmask = (1u << (8 * (dw - 4 * (j - 1)))) - 1u;
-        constexpr int FC_LB = 8;  // rows per thread in flight
-        for (int rb = r0; rb < nrows; rb += FC_LB * rstep) {  // ndw <= FC_NT (host: wider windows go to k_fast_cells_band)
-            // loads unconditional at clamped (in-window) addresses, the pads
-            // selected after them: a load behind a branch would have its
-            // result merged before the next one issues (a wait per row)
-            uint32_t lo[FC_LB], hi[FC_LB];
-            const int jc = min(max(j, 1), Ly.nq) - 1;
-#pragma unroll
-            for (int k = 0; k < FC_LB; k++) {
-                const int rc = min(max(rb + k * rstep, 1), dh) - 1;
-                const uint32_t* src = SCa + (long long)rc * lw4 + jc;
-                lo[k] = gfd::ldg(src);
-                hi[k] = gfd::ldg(src + 1);
-            }
-#pragma unroll
-            for (int k = 0; k < FC_LB; k++) {
-                const int r = rb + k * rstep;
-                const bool data = jdata && r >= 1 && r <= dh;
-                if (r < nrows && r0 < rstep)
-                    sc32[r * ndw + j] = data ? __builtin_amdgcn_alignbyte(hi[k], lo[k], sh) & bmask : 0u;
-            }
-        }
-    }
-    for (int i = tid; i < Ly.nwords; i += FC_NT) bits[i] = 0;
-    fc_sync();
-    int c = cell_nms4<FC_NW>(sc32, Ly, bits, dh, fast_th);
-    if ((tid & 63) == 0) s_cnt[0][tid >> 6] = c;
-    fc_sync();
-    int total = 0;
-#pragma unroll
-    for (int k = 0; k < FC_NW; k++) total += s_cnt[0][k];
-    if (total <= 3) {  // ORBextractor.cc:623-628: retry with the minimum threshold
-        // the ROI (window + 3-px ring margin) of the unblurred level to LDS
+    const int nq = retry[0];
+    for (int it = blockIdx.x; it < nq; it += gridDim.x) {
+        const int id = retry[1 + it], f = id / g.ncells, cid = id - f * g.ncells;
+        const CellInfo ci = cells[cid];
+        const int dw = ci.w - 6, dh = ci.h - 6, l = ci.level;
+        const FcLayout Ly = fc_layout(dw, dh, ci.w, ci.h);
+        uint8_t* sc = smem;  // window row y, column x at (y + 1) * pitch + 4 + x
+        uint32_t* sc32 = reinterpret_cast<uint32_t*>(smem);
+        uint32_t* bits = reinterpret_cast<uint32_t*>(smem + Ly.sc_bytes);  // window row y: words y * wpr ..
         uint8_t* roi = smem + Ly.sc_bytes + Ly.bits_bytes;
+        __syncthreads();  // the previous cell's listing has read the LDS
+        for (int i = tid; i < (dh + 2) * Ly.ndw; i += 256) sc32[i] = 0u;
+        for (int i = tid; i < Ly.nwords; i += 256) bits[i] = 0u;
         int sstride;
         const uint8_t* Sl = level_plane(P, g, f, l, sstride) + (long long)ci.y0 * sstride + ci.x0;
-        for (int i = tid; i < ci.w * ci.h; i += FC_NT) {
+        for (int i = tid; i < ci.w * ci.h; i += 256) {
             const int r = pyr_div(i, 1.0f / (float)ci.w);
             roi[i] = gfd::ldg(Sl + (long long)r * sstride + (i - r * ci.w));
         }
-        fc_sync();
-        for (int i = tid; i < dw * dh; i += FC_NT) {
+        __syncthreads();
+        for (int i = tid; i < dw * dh; i += 256) {
             const int y = pyr_div(i, 1.0f / (float)dw), x = i - y * dw;
             int cv[16];
             circle_vals(roi, ci.w, x + 3, y + 3, cv);
             const int M = fast_max_arc(roi[(y + 3) * ci.w + x + 3], cv);
             sc[(y + 1) * Ly.pitch + 4 + x] = M > min_th ? (uint8_t)M : 0;
         }
-        for (int i = tid; i < Ly.nwords; i += FC_NT) bits[i] = 0;
-        fc_sync();
-        c = cell_nms4<FC_NW>(sc32, Ly, bits, dh, min_th);
-        if ((tid & 63) == 0) s_cnt[1][tid >> 6] = c;
-        fc_sync();
-        total = 0;
-#pragma unroll
-        for (int k = 0; k < FC_NW; k++) total += s_cnt[1][k];
-    }
-    E* out = lists + (long long)f * list_stride + ci.cap_off;
-    const int X0 = ci.x0 + 3, Y0 = ci.y0 + 3;
-    int base = 0;
-    for (int w0 = 0; w0 < Ly.nwords; w0 += FC_NT) {  // words in row-major order: the survivors in FAST's order
-        const int i = w0 + tid;
-        uint32_t word = i < Ly.nwords ? bits[i] : 0u;
-        int tot;
-        int off;
-        if constexpr (FC_NT == 64) {
-            off = base + wave_scan_excl(__popc(word), tot);
-        } else {
-            off = base + block_scan_nw<FC_NW>(__popc(word), scan_tmp, tot);
-        }
-        if (word) {
-            const int y = i / Ly.wpr, xw = 32 * (i - y * Ly.wpr);
-            const uint8_t* srow = sc + (y + 1) * Ly.pitch + 4;
-            while (word) {
-                const int x = xw + __ffs(word) - 1;
-                word &= word - 1;
-                out[off++] = cell_entry<E>(srow[x] - 1, X0 + x, Y0 + y, P, g, f, l);
+        __syncthreads();
+        const int cw = cell_nms4<4>(sc32, Ly, bits, dh, min_th);
+        if ((tid & 63) == 0) s_cnt[tid >> 6] = cw;
+        __syncthreads();
+        const int total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        E* out = lists + (long long)f * list_stride + ci.cap_off;
+        const int X0 = ci.x0 + 3, Y0 = ci.y0 + 3;
+        int base = 0;
+        for (int w0 = 0; w0 < Ly.nwords; w0 += 256) {  // words in row-major order: the survivors in FAST's order
+            const int i = w0 + tid;
+            uint32_t word = i < Ly.nwords ? bits[i] : 0u;
+            int tot;
+            int off = base + block_scan_nw<4>(__popc(word), scan_tmp, tot);
+            if (word) {
+                const int y = i / Ly.wpr, xw = 32 * (i - y * Ly.wpr);
+                const uint8_t* srow = sc + (y + 1) * Ly.pitch + 4;
+                while (word) {
+                    const int x = xw + __ffs(word) - 1;
+                    word &= word - 1;
+                    out[off++] = cell_entry<E>(srow[x] - 1, X0 + x, Y0 + y, P, g, f, l);
+                }
             }
+            base += tot;
         }
-        base += tot;
+        if (tid == 0) counts[(long long)f * g.ncells + cid] = total;
     }
-    if (tid == 0) counts[(long long)f * g.ncells + cid] = total;
 }
 
 // One 256-thread workgroup per (large cell, frame): a cell window whose score
 // rows (and, for the minimum-threshold retry, ROI rows) do not fit
-// k_fast_cells' LDS — small nFeatures make few, large cells (ORBextractor.cc
-// :540-560 grids any level). The same FAST / NMS / listing as k_fast_cells,
+// k_cell_retry's LDS — small nFeatures make few, large cells (ORBextractor.cc
+// :540-560 grids any level). The same FAST / NMS / listing as the other cells',
 // with the window walked in bands of ci.band rows: each band's rows plus one
 // halo row either side go to LDS (the halo rows are what the 3x3 NMS of the
 // band's edge rows reads), the survivor bits of the whole window stay in LDS,
@@ -1235,12 +1467,6 @@ constexpr size_t sel_wave_lds() {
 // + the per-cell counts, quotas, offsets and flags of a level (maxnc cells at most)
 template <typename E>
 constexpr size_t sel_lds(int maxnc) { return sel_wave_lds<E>() + sizeof(int) * (3 * (size_t)maxnc + 1) + (size_t)maxnc; }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <typename E>
 __device__ __forceinline__ int sel_resp(E e) { return Ent<E>::key(e); }
@@ -1751,7 +1977,12 @@ struct gf_extractor {
     std::vector<int> feat_per_level;
     int capacity = 0;
     long long list_stride = 0, lvl_stride = 0;
-    size_t fast_lds = 0;
+    size_t fast_lds = 0;           // k_cell_retry's LDS (the largest window of a cell with band == 0)
+    int* d_retry = nullptr;        // k_cell_lists' retry queue: length, then f * ncells + cid entries
+    std::vector<int> level_cols;   // cell columns of each level's grid (cells in row-major order)
+    std::vector<NmsTask> nms_tasks;  // k_nms_tiles
+    NmsTask* d_nms_tasks = nullptr;
+    uint32_t *d_nms_xtab = nullptr, *d_surv = nullptr;  // column table; survivor plane (bslab / 8 bytes a frame)
     size_t band_lds = 0;           // k_fast_cells_band's LDS (0: no large cell)
     std::vector<int> band_cells;   // cells whose window takes the banded kernel
     int* d_band = nullptr;
@@ -1781,7 +2012,7 @@ static int cv_floor_f(float v) {
     return i - (i > v);
 }
 
-// k_fast_cells keeps a cell's whole window (score rows, retry ROI, survivor
+// k_cell_retry keeps a cell's whole window (score rows, ROI, survivor
 // bits) in LDS up to FC_LDS_MAX bytes; larger windows (small nFeatures) run
 // k_fast_cells_band within FC_BAND_LDS.
 constexpr size_t FC_LDS_MAX = 64 * 1024, FC_BAND_LDS = 120 * 1024;
@@ -1842,6 +2073,7 @@ static int plan_extractor(gf_extractor* ex) {
     ex->sel_maxnc = 0;
     ex->band_cells.clear();
     ex->band_lds = 0;
+    ex->level_cols.clear();
     long long cap_off = 0, lvl_off = 0;
     size_t max_lds = 0;
     const float imageRatio = (float)g.w[0] / g.h[0];
@@ -1861,6 +2093,7 @@ static int plan_extractor(gf_extractor* ex) {
         g.ndesired[l] = nDesired;
         g.cell_begin[l] = (int)ex->cells.size();
         g.lvl_off[l] = lvl_off;
+        ex->level_cols.push_back(levelCols);
         std::vector<int> iniXCol(levelCols, 0);
         float hY = cellH + 6;
         long long lvl_cap = 0;
@@ -1903,7 +2136,7 @@ static int plan_extractor(gf_extractor* ex) {
                         const size_t pitch = 4 * (size_t)((dw + 6) / 4), bits = 16 * (((size_t)dw * dh + 127) / 128);
                         const FcLayout fl = fc_layout(dw, dh, ci.w, ci.h);
                         const size_t lds = fl.total;
-                        if (lds <= FC_LDS_MAX && fl.ndw <= FC_NT) {
+                        if (lds <= FC_LDS_MAX && fl.ndw <= 256) {
                             max_lds = std::max(max_lds, lds);
                         } else {  // k_fast_cells_band: bands of BH rows (halo rows, ROI rows of the retry)
                             auto band_lds = [&](size_t bh) {
@@ -1934,6 +2167,81 @@ static int plan_extractor(gf_extractor* ex) {
     ex->fast_lds = max_lds;
     ex->capacity = 0;
     for (int l = 0; l < nl; l++) ex->capacity += ex->feat_per_level[l];
+    return GF_OK;
+}
+
+// k_nms_tiles' column table and tasks, from the cells' detection windows
+// (x0 + 3 .. x0 + w - 4, y0 + 3 .. y0 + h - 4 of every valid cell): the pixel
+// columns of cell column j and the pixel rows of cell row i. The kernel's
+// masks hold exactly when the windows of a level do not overlap and are the
+// product of those column and row ranges, which is checked here.
+static int nms_plan(gf_extractor* ex, std::vector<uint32_t>& xtab) {
+    const LevelGeom& g = ex->g;
+    ex->nms_tasks.clear();
+    xtab.clear();
+    for (int l = 0; l < g.nlevels; l++) {
+        const int w = g.w[l], h = g.h[l], pw = g.pw[l], cols = ex->level_cols[l];
+        std::vector<int> colid(pw + 1, -1), rowid(h + 1, -1);
+        for (int k = g.cell_begin[l]; k < g.cell_begin[l + 1]; k++) {
+            const CellInfo& ci = ex->cells[k];
+            const int i = (k - g.cell_begin[l]) / cols, j = (k - g.cell_begin[l]) % cols;
+            if (!ci.valid || ci.w - 6 <= 0 || ci.h - 6 <= 0) continue;
+            for (int x = ci.x0 + 3; x < ci.x0 + ci.w - 3; x++) {
+                GF_CHECK(x >= 0 && x < w && (colid[x] == -1 || colid[x] == j), GF_ERR_UNSUPPORTED,
+                         "cell windows overlap in x");
+                colid[x] = j;
+            }
+            for (int y = ci.y0 + 3; y < ci.y0 + ci.h - 3; y++) {
+                GF_CHECK(y >= 0 && y < h && (rowid[y] == -1 || rowid[y] == i), GF_ERR_UNSUPPORTED,
+                         "cell windows overlap in y");
+                rowid[y] = i;
+            }
+        }
+        for (int k = g.cell_begin[l]; k < g.cell_begin[l + 1]; k++) {
+            const CellInfo& ci = ex->cells[k];
+            const int i = (k - g.cell_begin[l]) / cols, j = (k - g.cell_begin[l]) % cols;
+            if (!ci.valid || ci.w - 6 <= 0 || ci.h - 6 <= 0) continue;
+            GF_CHECK(std::count(colid.begin(), colid.end(), j) == ci.w - 6 &&
+                         std::count(rowid.begin(), rowid.end(), i) == ci.h - 6,
+                     GF_ERR_UNSUPPORTED, "cell windows are not a product of column and row ranges");
+        }
+        const int xoff = (int)xtab.size(), nq = pw / 4;
+        for (int q = 0; q < nq; q++) {
+            uint32_t e = 0;
+            for (int b = 0; b < 4; b++) {
+                const int c = 4 * q + b;
+                if (colid[c] < 0) continue;
+                e |= 1u << b;
+                if (c >= 1 && colid[c - 1] == colid[c]) e |= 1u << (4 + b);
+                if (colid[c + 1] == colid[c]) e |= 1u << (8 + b);
+            }
+            xtab.push_back(e);
+        }
+        int ylo = 0, yhi = h;  // the rows of the level's window rows
+        while (ylo < h && rowid[ylo] < 0) ylo++;
+        while (yhi > ylo && rowid[yhi - 1] < 0) yhi--;
+        for (int q0 = 0; q0 < nq; q0 += 64) {
+            bool any = false;
+            for (int q = q0; q < std::min(q0 + 64, nq); q++) any = any || (xtab[xoff + q] & 15u);
+            if (!any) continue;
+            for (int y0 = ylo; y0 < yhi; y0 += NMS_ROWS) {
+                NmsTask t{};
+                t.level = l;
+                t.q0 = q0;
+                t.y0 = y0;
+                t.nrows = std::min(NMS_ROWS, yhi - y0);
+                t.xoff = xoff;
+                for (int r = 0; r < t.nrows; r++) {
+                    const int y = y0 + r;
+                    if (rowid[y] < 0) continue;
+                    t.in |= 1u << r;
+                    if (y >= 1 && rowid[y - 1] == rowid[y]) t.up |= 1u << r;
+                    if (rowid[y + 1] == rowid[y]) t.dn |= 1u << r;
+                }
+                ex->nms_tasks.push_back(t);
+            }
+        }
+    }
     return GF_OK;
 }
 
@@ -2044,6 +2352,10 @@ static void free_extractor(gf_extractor* ex) {
     (void)hipFree(ex->d_pyr);
     (void)hipFree(ex->d_blur);
     (void)hipFree(ex->d_score);
+    (void)hipFree(ex->d_surv);
+    (void)hipFree(ex->d_retry);
+    (void)hipFree(ex->d_nms_tasks);
+    (void)hipFree(ex->d_nms_xtab);
     (void)hipFree(ex->d_xtab);
     (void)hipFree(ex->d_ytab);
     (void)hipFree(ex->d_cells);
@@ -2136,6 +2448,12 @@ int gf_extractor_create(gf_ctx* ctx, int nfeatures, float scale_factor, int nlev
         delete ex;
         return rc;
     }
+    std::vector<uint32_t> nms_xtab;
+    rc = nms_plan(ex, nms_xtab);
+    if (rc) {
+        delete ex;
+        return rc;
+    }
     const LevelGeom& g = ex->g;
     auto cleanup = [&](hipError_t e) {
         free_extractor(ex);
@@ -2148,6 +2466,10 @@ int gf_extractor_create(gf_ctx* ctx, int nfeatures, float scale_factor, int nlev
     ALLOC(ex->d_pyr, std::max<long long>(g.slab, 256) * max_batch);
     ALLOC(ex->d_blur, g.bslab * max_batch);
     ALLOC(ex->d_score, g.bslab * max_batch);
+    ALLOC(ex->d_surv, g.bslab / 8 * max_batch);
+    ALLOC(ex->d_retry, sizeof(int) * ((size_t)g.ncells * max_batch + 1));
+    ALLOC(ex->d_nms_tasks, sizeof(NmsTask) * std::max<size_t>(ex->nms_tasks.size(), 1));
+    ALLOC(ex->d_nms_xtab, sizeof(uint32_t) * std::max<size_t>(nms_xtab.size(), 1));
     ALLOC(ex->d_cells, sizeof(CellInfo) * ex->cells.size());
     const size_t esz = ex->harris ? sizeof(uint64_t) : sizeof(uint32_t);
     ALLOC(ex->d_lists, esz * ex->list_stride * max_batch);
@@ -2265,20 +2587,28 @@ int gf_extractor_create(gf_ctx* ctx, int nfeatures, float scale_factor, int nlev
                                    (int)ex->pyr_lds));
     }
     GF_HIP(hipMemcpy(ex->d_cells, ex->cells.data(), sizeof(CellInfo) * ex->cells.size(), hipMemcpyHostToDevice));
+    // rows outside every window row are never written by k_nms_tiles: they hold 0 from here on
+    GF_HIP(hipMemset(ex->d_surv, 0, (size_t)(g.bslab / 8) * max_batch));
+    GF_HIP(hipMemset(ex->d_retry, 0, sizeof(int)));
+    if (!ex->nms_tasks.empty()) {
+        GF_HIP(hipMemcpy(ex->d_nms_tasks, ex->nms_tasks.data(), sizeof(NmsTask) * ex->nms_tasks.size(),
+                         hipMemcpyHostToDevice));
+        GF_HIP(hipMemcpy(ex->d_nms_xtab, nms_xtab.data(), sizeof(uint32_t) * nms_xtab.size(), hipMemcpyHostToDevice));
+    }
     if (!ex->band_cells.empty())
         GF_HIP(hipMemcpy(ex->d_band, ex->band_cells.data(), sizeof(int) * ex->band_cells.size(),
                          hipMemcpyHostToDevice));
     if (ex->harris) {
         GF_HIP(hipFuncSetAttribute((const void*)k_select_cells<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)(SEL_CW * sel_cell_wave_lds<uint64_t>(ex->sel_maxnc))));
-        GF_HIP(hipFuncSetAttribute((const void*)k_fast_cells<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        GF_HIP(hipFuncSetAttribute((const void*)k_cell_retry<uint64_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)ex->fast_lds));
         GF_HIP(hipFuncSetAttribute((const void*)k_fast_cells_band<uint64_t>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ex->band_lds));
     } else {
         GF_HIP(hipFuncSetAttribute((const void*)k_select_cells<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)(SEL_CW * sel_cell_wave_lds<uint32_t>(ex->sel_maxnc))));
-        GF_HIP(hipFuncSetAttribute((const void*)k_fast_cells<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        GF_HIP(hipFuncSetAttribute((const void*)k_cell_retry<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)ex->fast_lds));
         GF_HIP(hipFuncSetAttribute((const void*)k_fast_cells_band<uint32_t>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ex->band_lds));
@@ -2360,7 +2690,7 @@ static int extract_planes(gf_extractor* ex, int nframes, Planes P, gf_keypoint* 
                       : select_describe<uint32_t>(ex, nframes, P, d_kps, d_desc, d_counts, cap, s);
 }
 
-// k_fast_cells (+ k_fast_cells_band), k_select, k_describe on list entries E.
+// k_nms_tiles, k_cell_lists, k_cell_retry (+ k_fast_cells_band), k_select, k_describe on list entries E.
 template <typename E>
 static int select_describe(gf_extractor* ex, int nframes, Planes P, gf_keypoint* d_kps, uint8_t* d_desc,
                            int32_t* d_counts, int cap, hipStream_t s) {
@@ -2370,8 +2700,17 @@ static int select_describe(gf_extractor* ex, int nframes, Planes P, gf_keypoint*
     E* lvl = reinterpret_cast<E*>(ex->d_lvl);
     {
         GF_PROF(ctx, s, "k_fast_cells");
-        GF_LAUNCH(k_fast_cells<E>, dim3(g.ncells, nframes), FC_NT, ex->fast_lds, s, P, g, ex->d_score, ex->d_cells,
-                  lists, ex->list_stride, ex->d_counts, ex->fast_th, ex->min_th);
+        if (!ex->nms_tasks.empty())
+            GF_LAUNCH(k_nms_tiles, dim3(((int)ex->nms_tasks.size() + 3) / 4, nframes), 256, 0, s, g, ex->d_score,
+                      ex->d_nms_tasks, (int)ex->nms_tasks.size(), ex->d_nms_xtab, ex->d_surv, ex->fast_th,
+                      ex->d_retry);
+        GF_LAUNCH(k_cell_lists<E>, dim3((g.ncells + 3) / 4, nframes), 256, 0, s, P, g, ex->d_score, ex->d_surv,
+                  ex->d_cells, lists, ex->list_stride, ex->d_counts, ex->d_retry);
+        // the queued cells' retry: workgroups take queue entries in turn (a queue of any length)
+        if (ex->fast_lds)
+            GF_LAUNCH(k_cell_retry<E>, dim3((unsigned)std::min<long long>((long long)g.ncells * nframes, 2048)), 256,
+                      ex->fast_lds, s, P, g, ex->d_cells, lists, ex->list_stride, ex->d_counts, ex->d_retry,
+                      ex->min_th);
         if (!ex->band_cells.empty())
             GF_LAUNCH(k_fast_cells_band<E>, dim3((int)ex->band_cells.size(), nframes), 256, ex->band_lds, s, P, g,
                       ex->d_score, ex->d_cells, ex->d_band, lists, ex->list_stride, ex->d_counts, ex->fast_th,
