@@ -50,6 +50,13 @@ all: $(SELCHECK)
 $(SELCHECK): tests/helpers/select_check.cpp $(CSRC)/select.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared $< -o $@
 
+# the tests' CPU restatement of Sim3Solver (tests/test_sim3.py): oracle-style
+# flags, no vectorisation, no contraction
+SIM3REF = tests/helpers/libsim3ref.so
+all: $(SIM3REF)
+$(SIM3REF): tests/helpers/sim3_ref.cpp include/gfslam/abi.h
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

@@ -130,6 +130,10 @@ _PROTOS = {
     "gf_pnp_init": [_I, _P, _P],
     "gf_pnp_iterate": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "gf_pnp_iterate_dev": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gf_sim3_init": [_I, _P, _P],
+    "gf_sim3_iterate": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "gf_sim3_iterate_dev": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gf_search_by_sim3": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _F, _P, _P, _F, _P],
     "gf_local_ba": [_P, _P, _P],
     "gf_ba_plan_create": [_P, _I, _P, _P],
     "gf_ba_plan_solve": [_P, _P, _P],

@@ -1,0 +1,221 @@
+"""Loop-closure Sim3: the reference's ``ORB_SLAM::Sim3Solver``
+(include/Sim3Solver.h, src/Sim3Solver.cc) on the device, Horn's closed form on
+random three-point sets inside RANSAC, behind ``gf_sim3_init`` /
+``gf_sim3_iterate`` / ``gf_sim3_iterate_dev`` (include/gfslam/abi.h).
+
+``Sim3Solver`` keeps the reference's interface: built from two keyframes and
+the map points of the second matched to the first's keypoints (ctor :40-112;
+NULL, bad and unindexed points skipped), ``set_ransac_parameters`` (:114-138),
+``iterate(n)`` (:140-207) returning ``(T12 or None, no_more, inliers,
+n_inliers)`` with ``inliers`` indexed by KF1 keypoint like the reference's
+``vbInliers``, ``find()`` (:209-213) and the three ``estimated_*`` getters. The
+process-wide ``std::rand()`` of the reference is the :class:`Rand` of
+``pnp.py``, shared by the solvers of one ``ComputeSim3`` round robin
+(LoopClosing.cc:300-352).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from ._lib import check, lib, ptr
+from .matcher import default_context
+from .pnp import Rand  # noqa: F401  (re-exported: the solvers' shared rand())
+
+SIM3_PARAMS_DTYPE = np.dtype([("probability", "f8"), ("min_inliers", "i4"), ("max_iterations", "i4")], align=True)
+SIM3_STATE_DTYPE = np.dtype([("n", "i4"), ("min_inliers", "i4"), ("max_iterations", "i4"), ("iterations", "i4"),
+                             ("best_inliers", "i4"), ("best_scale", "f4"), ("best_R", "f4", (9,)),
+                             ("best_t", "f4", (3,)), ("best_T12", "f4", (16,))], align=True)
+GF_SIM3_FOUND, GF_SIM3_NOMORE, GF_SIM3_TRUNCATED = 1, 2, 8
+
+assert SIM3_PARAMS_DTYPE.itemsize == 16 and SIM3_STATE_DTYPE.itemsize == 136
+
+
+def sim3_params(probability=0.99, min_inliers=6, max_iterations=300):
+    """SetRansacParameters arguments; the defaults are Sim3Solver.h's."""
+    p = np.zeros(1, SIM3_PARAMS_DTYPE)
+    p[0] = (probability, min_inliers, max_iterations)
+    return p
+
+
+@dataclass
+class Sim3KeyFrame:
+    """What the solver reads of a KeyFrame: pose, undistorted keypoints, the
+    slot -> map point id table (-1 = NULL), calibration and level sigma^2."""
+    Tcw: np.ndarray
+    kps: np.ndarray
+    mp_ids: np.ndarray
+    K: tuple
+    level_sigma2: np.ndarray
+
+    def index_of(self, mp_id: int) -> int:
+        """MapPoint::GetIndexInKeyFrame: the slot that holds the point, or -1.
+        A map point id occurs at most once per keyframe."""
+        hit = np.nonzero(np.asarray(self.mp_ids) == mp_id)[0]
+        return int(hit[0]) if len(hit) else -1
+
+
+def _to_camera(Tcw, Xw):
+    """Rcw*Xw + tcw in float32, products summed left to right (assumption A1)."""
+    T = np.asarray(Tcw, np.float32).reshape(4, 4)
+    X = np.asarray(Xw, np.float32)
+    out = np.empty(3, np.float32)
+    for r in range(3):
+        acc = np.float32(T[r, 0] * X[0])
+        acc = np.float32(acc + np.float32(T[r, 1] * X[1]))
+        acc = np.float32(acc + np.float32(T[r, 2] * X[2]))
+        out[r] = np.float32(acc + T[r, 3])
+    return out
+
+
+def search_by_sim3(info, kf1, desc1, kf2, desc2, mps, mp_desc, matches12, s12, R12, t12, th=7.5, mp_bad=None,
+                   ctx=None):
+    """ORBmatcher::SearchBySim3 (ORBmatcher.cc:1841-2079) over
+    ``gf_search_by_sim3``. info: the FrameInfo both keyframes share; kf1 / kf2:
+    :class:`Sim3KeyFrame`; desc1 / desc2: their [n, 32] descriptors; mps
+    (MAP_POINT_DTYPE), mp_desc, mp_bad: the map the slot tables index;
+    matches12: per KF1 keypoint the KF2 map point matched so far (-1 = NULL).
+    -> (matches12 with the new matches added, nfound)."""
+    import ctypes
+
+    ctx = ctx or default_context()
+    m12 = np.ascontiguousarray(matches12, np.int32).copy()
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    T1, T2 = c(kf1.Tcw, np.float32).reshape(16), c(kf2.Tcw, np.float32).reshape(16)
+    k1, k2 = c(kf1.kps, kf1.kps.dtype), c(kf2.kps, kf2.kps.dtype)
+    d1, d2 = c(desc1, np.uint8), c(desc2, np.uint8)
+    i1, i2 = c(kf1.mp_ids, np.int32), c(kf2.mp_ids, np.int32)
+    mp, md = c(mps, mps.dtype), c(mp_desc, np.uint8)
+    bad = None if mp_bad is None else c(np.asarray(mp_bad).astype(np.uint8), np.uint8)
+    R, t = c(R12, np.float32).reshape(9), c(t12, np.float32).reshape(3)
+    nf = ctypes.c_int(0)
+    check(lib().gf_search_by_sim3(ctx.handle, ctypes.byref(info), ptr(T1), ptr(k1), ptr(d1), len(k1), ptr(i1),
+                                  ptr(T2), ptr(k2), ptr(d2), len(k2), ptr(i2), ptr(mp), ptr(md), ptr(bad), len(mp),
+                                  ptr(m12), float(s12), ptr(R), ptr(t), float(th), ctypes.byref(nf)))
+    return m12, int(nf.value)
+
+
+class Sim3Solver:
+    def __init__(self, kf1: Sim3KeyFrame, kf2: Sim3KeyFrame, matched12, mp_pos, mp_bad=None, ctx=None):
+        """matched12: per KF1 keypoint, the id of the KF2 map point matched to
+        it (-1 = NULL); mp_pos: [n_mp, 3] world positions; mp_bad: isBad()."""
+        self.ctx = ctx or default_context()
+        matched12 = np.asarray(matched12, np.int32)
+        mp_pos = np.asarray(mp_pos, np.float32).reshape(-1, 3)
+        bad = np.zeros(len(mp_pos), bool) if mp_bad is None else np.asarray(mp_bad, bool)
+        self.n_kps = len(matched12)  # mN1
+        idx1, X1, X2, s1, s2 = [], [], [], [], []
+        for i1 in range(self.n_kps):
+            mp2 = int(matched12[i1])
+            if mp2 < 0:
+                continue
+            mp1 = int(kf1.mp_ids[i1])
+            if mp1 < 0 or bad[mp1] or bad[mp2]:
+                continue
+            k1, k2 = kf1.index_of(mp1), kf2.index_of(mp2)
+            if k1 < 0 or k2 < 0:
+                continue
+            s1.append(kf1.level_sigma2[kf1.kps["octave"][k1]])
+            s2.append(kf2.level_sigma2[kf2.kps["octave"][k2]])
+            idx1.append(i1)  # mvnIndices1
+            X1.append(_to_camera(kf1.Tcw, mp_pos[mp1]))
+            X2.append(_to_camera(kf2.Tcw, mp_pos[mp2]))
+        self.kp_idx = np.asarray(idx1, np.int32)
+        self.X1 = np.ascontiguousarray(np.asarray(X1, np.float32).reshape(-1, 3))
+        self.X2 = np.ascontiguousarray(np.asarray(X2, np.float32).reshape(-1, 3))
+        self.sigma2_1 = np.ascontiguousarray(s1, np.float32)
+        self.sigma2_2 = np.ascontiguousarray(s2, np.float32)
+        self.K1 = np.asarray(kf1.K, np.float32).reshape(4)
+        self.K2 = np.asarray(kf2.K, np.float32).reshape(4)
+        self.best_mask = np.zeros(max(self.N, 1), np.uint8)
+        self.set_ransac_parameters()
+
+    @property
+    def N(self) -> int:
+        return len(self.X1)
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=6, max_iterations=300):
+        # SetRansacParameters (:114-138) resets mnIterations and leaves the
+        # best hypothesis as it is: keep it across a re-call
+        old = getattr(self, "state", None)
+        self.state = np.zeros(1, SIM3_STATE_DTYPE)
+        check(lib().gf_sim3_init(self.N, ptr(sim3_params(probability, min_inliers, max_iterations)), ptr(self.state)))
+        if old is not None:
+            for k in ("best_inliers", "best_scale", "best_R", "best_t", "best_T12"):
+                self.state[k] = old[k]
+
+    def iterate(self, n_iterations: int, rng: Rand):
+        T = np.zeros(16, np.float32)
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        ninl = np.zeros(1, np.int32)
+        fl = np.zeros(1, np.int32)
+        check(lib().gf_sim3_iterate(self.ctx.handle, ptr(self.X1), ptr(self.X2), ptr(self.sigma2_1),
+                                    ptr(self.sigma2_2), ptr(self.K1), ptr(self.K2), ptr(self.state),
+                                    ptr(self.best_mask), int(n_iterations), ptr(rng.state), ptr(T), ptr(inl),
+                                    ptr(ninl), ptr(fl)))
+        vb = np.zeros(self.n_kps, bool)
+        vb[self.kp_idx[inl[:self.N].astype(bool)]] = True
+        T12 = T.reshape(4, 4) if fl[0] & GF_SIM3_FOUND else None
+        return T12, bool(fl[0] & GF_SIM3_NOMORE), vb, int(ninl[0])
+
+    def find(self, rng: Rand):
+        T12, _, vb, ninl = self.iterate(int(self.state["max_iterations"][0]), rng)
+        return T12, vb, ninl
+
+    def estimated_rotation(self):
+        return self.state["best_R"][0].reshape(3, 3).copy()
+
+    def estimated_translation(self):
+        return self.state["best_t"][0].copy()
+
+    def estimated_scale(self) -> float:
+        return float(self.state["best_scale"][0])
+
+
+def compute_sim3(info, current, candidates, mps, mp_desc, rand: Rand, mp_bad=None, ctx=None):
+    """LoopClosing::ComputeSim3 (LoopClosing.cc:261-352) up to, but not
+    including, Optimizer::OptimizeSim3. current and each candidate are
+    ``(Sim3KeyFrame, descriptors, FeatureVector)``. Per candidate:
+    SearchByBoW(KF, KF) with ORBmatcher(0.75, true), discarded under 20 matches;
+    SetRansacParameters(0.99, 20, 300); then iterate(5) round robin on the host
+    entry point, one solver at a time, so the shared rand() interleaves as the
+    reference's does; a candidate whose solver reports bNoMore is discarded. The
+    first Sim3 a solver returns ends the loop (the reference goes on only when
+    OptimizeSim3 rejects it): its inlier-only match vector goes through
+    SearchBySim3(..., 7.5). -> one dict per candidate: ``T12`` (4x4 or None),
+    ``s``, ``R``, ``t``, ``matches`` (per current keypoint, -1 = NULL),
+    ``n_inliers``, ``discarded`` (None, "few_matches" or "no_more")."""
+    from .bow import search_by_bow
+
+    ctx = ctx or default_context()
+    kf_c, desc_c, fv_c = current
+    res = [dict(T12=None, s=None, R=None, t=None, matches=None, n_inliers=0, discarded=None) for _ in candidates]
+    solvers, bow = {}, {}
+    for i, (kf, desc, fv) in enumerate(candidates):
+        nm, m12 = search_by_bow(1, 0.75, True, (fv_c, desc_c, kf_c.kps, kf_c.mp_ids), (fv, desc, kf.kps, kf.mp_ids),
+                                ctx)
+        if nm < 20:
+            res[i]["discarded"] = "few_matches"
+            continue
+        bow[i] = m12
+        solvers[i] = Sim3Solver(kf_c, kf, m12, mps["pos"], mp_bad, ctx)
+        solvers[i].set_ransac_parameters(0.99, 20, 300)
+    active = len(solvers)
+    while active > 0:
+        for i in sorted(solvers):
+            if res[i]["discarded"]:
+                continue
+            T12, no_more, vb, ninl = solvers[i].iterate(5, rand)
+            if no_more:
+                res[i]["discarded"] = "no_more"
+                active -= 1
+            if T12 is not None:
+                kf, desc, _ = candidates[i]
+                s, Rm, t = solvers[i].estimated_scale(), solvers[i].estimated_rotation(), \
+                    solvers[i].estimated_translation()
+                m = np.where(vb, bow[i], -1).astype(np.int32)
+                m, _ = search_by_sim3(info, kf_c, desc_c, kf, desc, mps, mp_desc, m, s, Rm, t, 7.5, mp_bad, ctx)
+                res[i].update(T12=T12, s=s, R=Rm, t=t, matches=m, n_inliers=ninl)
+                return res
+    return res

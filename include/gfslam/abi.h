@@ -745,6 +745,80 @@ int gf_pnp_iterate_dev(gf_ctx* ctx, int nprob, const float* d_p3d, const float* 
                        int max_iterations, gf_rng* d_rng, float* d_Tcw, uint8_t* d_inliers, int32_t* d_ninliers,
                        int32_t* d_flags, void* stream);
 
+/* ------------------------------------------------ loop-closure Sim3 solver
+ * ORB_SLAM::Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h): Horn's
+ * closed-form absolute orientation on random three-point sets inside RANSAC;
+ * LoopClosing::ComputeSim3 drives it (LoopClosing.cc:261-352:
+ * SetRansacParameters(0.99,20,300), then iterate(5) per candidate keyframe,
+ * round robin). A problem is the solver's correspondence list after the
+ * constructor's filtering (:62-103), in that order: X1, X2 (n x 3, the matched
+ * map points in camera 1 / camera 2 coordinates), sigma2_1, sigma2_2 (level
+ * sigma^2 of the two keypoints), K1, K2 = (fx, fy, cx, cy). The keypoint-index
+ * mapping (mvnIndices1) stays with the caller. */
+typedef struct gf_sim3_params { /* SetRansacParameters arguments (:114) */
+    double probability;
+    int32_t min_inliers;
+    int32_t max_iterations;
+} gf_sim3_params;
+typedef struct gf_sim3_state { /* one solver across iterate() calls */
+    int32_t n;              /* N correspondences */
+    int32_t min_inliers;    /* mRansacMinInliers */
+    int32_t max_iterations; /* mRansacMaxIts after the adjustment (:125-135) */
+    int32_t iterations;     /* mnIterations */
+    int32_t best_inliers;   /* mnBestInliers */
+    float best_scale;       /* mBestScale */
+    float best_R[9];        /* mBestRotation, row-major */
+    float best_t[3];        /* mBestTranslation */
+    float best_T12[16];     /* mBestT12, row-major */
+} gf_sim3_state;
+#define GF_SIM3_FOUND 1     /* iterate returned a Sim3                         */
+#define GF_SIM3_NOMORE 2    /* bNoMore                                         */
+#define GF_SIM3_TRUNCATED 8 /* device path: max_iterations cut the call's loop short */
+/* Sim3Solver::SetRansacParameters (host scalar set-up) into a fresh state:
+ * iteration count 0, no best hypothesis. Where the reference converts a NaN or
+ * out-of-range iteration estimate to int, max_iterations is taken. */
+int gf_sim3_init(int n, const gf_sim3_params* params, gf_sim3_state* state);
+/* Sim3Solver::iterate(nIterations, bNoMore, vbInliers, nInliers) (:140-207)
+ * for one solver; rng is the process-wide std::rand() state the minimal sets
+ * are drawn from (DUtils::Random::RandomInt, :168), advanced by three draws
+ * per iteration run. best_mask (n bytes, mvbBestInliers) persists across calls
+ * with the state; the best hypothesis is replaced on >=, so it can hold the
+ * NaN transform of a degenerate set. Outputs: T12 (row-major, valid when
+ * flags & FOUND, else zeros), inliers (n bytes, correspondence order),
+ * ninliers, flags. */
+int gf_sim3_iterate(gf_ctx* ctx, const float* X1, const float* X2, const float* sigma2_1, const float* sigma2_2,
+                    const float K1[4], const float K2[4], gf_sim3_state* state, uint8_t* best_mask, int n_iterations,
+                    gf_rng* rng, float T12[16], uint8_t* inliers, int32_t* ninliers, int32_t* flags);
+/* Device batch: nprob independent solvers, problem b's correspondences at
+ * [b][cap] of d_X1, d_X2, d_sigma2_1, d_sigma2_2, d_best_mask, d_inliers, its size in
+ * d_state[b].n; each problem draws from its own d_rng[b]. d_T12 is [nprob][16].
+ * max_iterations bounds the iterations of this call; a problem whose loop it
+ * cuts short before a Sim3 is found gets GF_SIM3_TRUNCATED. States are clamped
+ * on the device (n to cap). Asynchronous on `stream`. */
+int gf_sim3_iterate_dev(gf_ctx* ctx, int nprob, const float* d_X1, const float* d_X2, const float* d_sigma2_1,
+                        const float* d_sigma2_2, int cap, const float K1[4], const float K2[4],
+                        gf_sim3_state* d_state, uint8_t* d_best_mask, int n_iterations, int max_iterations,
+                        gf_rng* d_rng, float* d_T12, uint8_t* d_inliers, int32_t* d_ninliers, int32_t* d_flags,
+                        void* stream);
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
+ * (ORBmatcher.cc:1841-2079) for one keyframe pair, host arrays: KF1's
+ * unmatched map points are projected into KF2 with (sR21, t21), KF2's into KF1
+ * with (sR12, t12); a pair of keypoints that chose each other becomes a match.
+ * Both passes use fi's intrinsics, image bounds and scale factors (the
+ * reference takes KF1's, :1844-1847). Per keyframe: Tcw (row-major 4x4), kps
+ * (undistorted), desc (n x 32), n <= 4096, kf_mp (slot -> index into
+ * mps/mp_desc/mp_bad, or -1: GetMapPointMatches). matches12 (n1, in and out)
+ * holds map point indices of KF2's points, -1 = NULL; entries that come in set
+ * are left as they are. GetIndexInKeyFrame(pKF2) of an incoming match is read
+ * as the slot of kf_mp2 that holds it: a map point occurs at most once per
+ * keyframe. KeyFrame::GetFeaturesInArea order decides ties (cell column outer,
+ * row inner, keypoint index ascending in a cell). nfound: matches added. */
+int gf_search_by_sim3(gf_ctx* ctx, const gf_frame_info* fi, const float* Tcw1, const gf_keypoint* kps1,
+                      const uint8_t* desc1, int n1, const int32_t* kf_mp1, const float* Tcw2, const gf_keypoint* kps2,
+                      const uint8_t* desc2, int n2, const int32_t* kf_mp2, const gf_map_point* mps,
+                      const uint8_t* mp_desc, const uint8_t* mp_bad, int nmp, int32_t* matches12, float s12,
+                      const float R12[9], const float t12[3], float th, int* nfound);
+
 /* ------------------------------------------------ monocular initialisation
  * ORB_SLAM::Initializer (src/Initializer.cc, include/Initializer.h):
  * Initializer(ReferenceFrame, sigma, iterations) + Initialize(CurrentFrame,
