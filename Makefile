@@ -57,6 +57,13 @@ all: $(SIM3REF)
 $(SIM3REF): tests/helpers/sim3_ref.cpp include/gfslam/abi.h
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of OptimizeSim3 and of the Sim3 projection search
+# (tests/test_sim3_optimize.py), same flags
+SIM3OPTREF = tests/helpers/libsim3optref.so
+all: $(SIM3OPTREF)
+$(SIM3OPTREF): tests/helpers/sim3opt_ref.cpp include/gfslam/abi.h
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

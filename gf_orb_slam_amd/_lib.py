@@ -134,6 +134,9 @@ _PROTOS = {
     "gf_sim3_iterate": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "gf_sim3_iterate_dev": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "gf_search_by_sim3": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _F, _P, _P, _F, _P],
+    "gf_optimize_sim3": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P],
+    "gf_optimize_sim3_dev": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "gf_search_kf_sim3_projection": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P],
     "gf_local_ba": [_P, _P, _P],
     "gf_ba_plan_create": [_P, _I, _P, _P],
     "gf_ba_plan_solve": [_P, _P, _P],

@@ -308,4 +308,147 @@ SE3_HD bool ldlt6(const double* Ain, const double* b, double* x) {
     return true;
 }
 
+// The same factorisation for the 7x7 system of the Sim3 vertex
+// (Optimizer::OptimizeSim3: one VertexSim3Expmap behind LinearSolverDense).
+// A port of ldlt6 with the size as a constant of its own: ldlt6 and its
+// results are untouched.
+namespace ldlt7_detail {
+constexpr int N = 7;
+using ldlt_detail::csw;
+
+template <int K, int B>
+SE3_HD void sym_swap(double (&A)[N * N], bool c) {
+#pragma unroll
+    for (int j = 0; j < K; j++) csw(c, A[K * N + j], A[B * N + j]);
+#pragma unroll
+    for (int i = B + 1; i < N; i++) csw(c, A[i * N + K], A[i * N + B]);
+    csw(c, A[K * (N + 1)], A[B * (N + 1)]);
+#pragma unroll
+    for (int i = K + 1; i < B; i++) csw(c, A[i * N + K], A[B * N + i]);
+}
+
+template <int K, int B>
+SE3_HD void pivot(double (&A)[N * N], int big) {
+    if constexpr (B < N) {
+        sym_swap<K, B>(A, big == B);
+        pivot<K, B + 1>(A, big);
+    }
+}
+
+template <int K, int B>
+SE3_HD void perm_vec(double (&y)[N], int p) {
+    if constexpr (B < N) {
+        csw(p == B, y[K], y[B]);
+        perm_vec<K, B + 1>(y, p);
+    }
+}
+
+template <int K>
+SE3_HD void step(double (&A)[N * N], int (&perm)[N], int& sign, bool& stop) {
+    if constexpr (K < N) {
+        int big = K;
+        double bv = fabs(A[K * (N + 1)]);
+#pragma unroll
+        for (int i = K + 1; i < N; i++)
+            if (fabs(A[i * (N + 1)]) > bv) bv = fabs(A[i * (N + 1)]), big = i;
+        perm[K] = big;
+        pivot<K, K + 1>(A, big);
+        if constexpr (K > 0) {
+            double temp[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) temp[j] = A[j * (N + 1)] * A[K * N + j];
+            double s = 0;
+#pragma unroll
+            for (int j = 0; j < K; j++) s += A[K * N + j] * temp[j];
+            A[K * (N + 1)] -= s;
+#pragma unroll
+            for (int i = K + 1; i < N; i++) {
+                double t = 0;
+#pragma unroll
+                for (int j = 0; j < K; j++) t += A[i * N + j] * temp[j];
+                A[i * N + K] -= t;
+            }
+        }
+        const double akk = A[K * (N + 1)];
+        const bool valid = fabs(akk) > 0;
+        if (K == 0 && !valid) {  // zero matrix: identity transpositions, ZeroSign
+            sign = 0;
+#pragma unroll
+            for (int j = 0; j < N; j++) perm[j] = j;
+            stop = true;
+            return;
+        }
+        if (valid) {
+#pragma unroll
+            for (int i = K + 1; i < N; i++) A[i * N + K] /= akk;
+        }
+        if (sign == 1) {
+            if (akk < 0) sign = 3;
+        } else if (sign == 2) {
+            if (akk > 0) sign = 3;
+        } else if (sign == 0) {
+            if (akk > 0)
+                sign = 1;
+            else if (akk < 0)
+                sign = 2;
+        }
+        step<K + 1>(A, perm, sign, stop);
+    }
+}
+
+template <int K>
+SE3_HD void perm_fwd(double (&y)[N], const int (&perm)[N]) {
+    if constexpr (K < N - 1) {
+        perm_vec<K, K + 1>(y, perm[K]);
+        perm_fwd<K + 1>(y, perm);
+    }
+}
+
+template <int K>
+SE3_HD void perm_bwd(double (&y)[N], const int (&perm)[N]) {
+    if constexpr (K >= 0) {
+        perm_vec<K, K + 1>(y, perm[K]);
+        perm_bwd<K - 1>(y, perm);
+    }
+}
+
+}  // namespace ldlt7_detail
+
+// A row-major 7x7 (lower triangle read), b and x of 7; see ldlt6.
+SE3_HD bool ldlt7(const double* Ain, const double* b, double* x) {
+    constexpr int N = ldlt7_detail::N;
+    double A[N * N];
+#pragma unroll
+    for (int i = 0; i < N * N; i++) A[i] = Ain[i];
+    int perm[N];
+    int sign = 0;  // 0 zero, 1 psd, 2 nsd, 3 indefinite
+    bool stop = false;
+    ldlt7_detail::step<0>(A, perm, sign, stop);
+    if (!(sign == 1 || sign == 0)) return false;
+    double y[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) y[i] = b[i];
+    ldlt7_detail::perm_fwd<0>(y, perm);  // y = P b
+    // L^-1 (unit lower, column axpy order)
+#pragma unroll
+    for (int j = 0; j < N; j++)
+#pragma unroll
+        for (int i = j + 1; i < N; i++) y[i] -= A[i * N + j] * y[j];
+    // D^+ (pseudo-inverse below numeric_limits<double>::min())
+#pragma unroll
+    for (int i = 0; i < N; i++) y[i] = fabs(A[i * (N + 1)]) > DBL_MIN ? y[i] / A[i * (N + 1)] : 0.0;
+    // L^-T
+#pragma unroll
+    for (int i = N - 1; i >= 0; i--) {
+        double s = 0;
+#pragma unroll
+        for (int k = i + 1; k < N; k++) s += A[k * N + i] * y[k];
+        y[i] -= s;
+    }
+    ldlt7_detail::perm_bwd<N - 2>(y, perm);  // P^-1
+#pragma unroll
+    for (int i = 0; i < N; i++) x[i] = y[i];
+    return true;
+}
+
 }  // namespace gfse3

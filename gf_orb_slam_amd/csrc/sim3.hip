@@ -275,9 +275,235 @@ __global__ __launch_bounds__(MATCH_THREADS) void k_search_sim3(FrameConst fc, Si
     if (tid == 0) *nfound = s_nf;
 }
 
+// ------------------------------------------- SearchByProjection(pKF, Scw, ...)
+// ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+// (ORBmatcher.cc:855-977) by one 1024-thread workgroup. The reference walks
+// the candidates in list order and writes vpMatched[bestIdx] inside the loop,
+// so a keypoint taken by an earlier candidate is gone for the later ones. That
+// is a serial dictatorship, which equals the one stable assignment when every
+// keypoint prefers the lower candidate index and every candidate orders the
+// keypoints of its window by (distance, GetFeaturesInArea position), cut at
+// TH_LOW. The rounds below reach it by deferred acceptance: owner[k] is the
+// lowest candidate that has asked for keypoint k so far and only ever
+// decreases; a candidate that does not hold its keypoint searches again among
+// the keypoints whose owner is above it. A candidate's choice set only
+// shrinks, so a keypoint it holds stays its best, and one that finds nothing
+// is done. Each round with a request lowers an owner: at most m + 1 rounds.
+#define SP_TH_LOW 50
+
+struct ProjCand {
+    float u, v, r;
+    int32_t lvl;  // predicted level, -1: the candidate left at one of the exits
+};
+
+struct ProjArgs {
+    float T[12];  // Rcw | tcw of the decomposed Scw
+    float Ow[3];
+    const gf_keypoint* kps;
+    const uint8_t* desc;
+    int32_t n;
+    const gf_map_point* mps;
+    const uint8_t* mp_desc;
+    const uint8_t* mp_bad;
+    int32_t nmp;
+    const int32_t* points;  // vpPoints: map point ids, list order
+    int32_t m;
+    int32_t* matched;  // vpMatched, in and out
+    uint8_t* mark;     // nmp bytes, zeroed: spAlreadyFound
+    ProjCand* cand;    // m
+    int32_t* cur;      // m: the keypoint candidate i asked for, -1 none yet, -2 nothing left
+    float th;
+    int32_t* nmatches;
+};
+
+__global__ __launch_bounds__(MATCH_THREADS) void k_search_proj_sim3(FrameConst fc, ProjArgs P) {
+    extern __shared__ int lds[];
+    const int tid = threadIdx.x, n = P.n, m = P.m;
+    int* cell_start = lds;                 // NCELLS + 1
+    int* items = cell_start + NCELLS + 1;  // n
+    int* owner = items + n;                // n
+    int* scratch = owner + n;              // n
+    __shared__ int s_req, s_nm;
+    if (tid == 0) s_nm = 0;
+    build_grid(fc, P.kps, n, P.matched, cell_start, items, owner, scratch, MATCH_THREADS);
+    // spAlreadyFound (:874-875) is built once, before the loop
+    for (int k = tid; k < n; k += MATCH_THREADS) {
+        const int id = owner[k];
+        if (id >= 0 && id < P.nmp) P.mark[id] = 1;
+        owner[k] = id >= 0 ? -1 : INT_MAX;  // vpMatched[idx] set at entry: taken for everyone
+    }
+    __syncthreads();
+    const int nmax = fc.nlevels - 1;
+    // the exits that do not depend on the claims (:882-937, window part)
+    for (int i = tid; i < m; i += MATCH_THREADS) {
+        ProjCand c{0.f, 0.f, 0.f, -1};
+        do {
+            const int id = P.points[i];
+            if (id < 0 || id >= P.nmp) break;
+            if ((P.mp_bad && P.mp_bad[id]) || P.mark[id]) break;
+            const gf_map_point mp = P.mps[id];
+            float Pc[3];
+            transform3(P.T, mp.pos, Pc);
+            if (Pc[2] < 0.0f) break;
+            const float invz = 1.f / Pc[2];
+            const float x = Pc[0] * invz, y = Pc[1] * invz;
+            const float u = fc.fx * x + fc.cx, v = fc.fy * y + fc.cy;
+            if (!(u >= (float)fc.min_x && u < (float)fc.max_x && v >= (float)fc.min_y && v < (float)fc.max_y)) break;
+            const float PO[3] = {mp.pos[0] - P.Ow[0], mp.pos[1] - P.Ow[1], mp.pos[2] - P.Ow[2]};
+            // cv::norm / Mat::dot accumulate in double
+            const float dist = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
+            if (dist < mp.min_dist || dist > mp.max_dist) break;
+            const double dot = (double)PO[0] * mp.normal[0] + (double)PO[1] * mp.normal[1] + (double)PO[2] * mp.normal[2];
+            if (dot < 0.5 * (double)dist) break;
+            const float ratio = dist / mp.min_dist;
+            int lvl = 0;
+            while (lvl < fc.nlevels && fc.scales[lvl] < ratio) lvl++;  // lower_bound
+            lvl = min(lvl, nmax);
+            c = ProjCand{u, v, P.th * fc.scales[lvl], lvl};
+        } while (false);
+        P.cand[i] = c;
+        P.cur[i] = -1;
+    }
+    __syncthreads();
+    for (int round = 0; round <= m; round++) {
+        if (tid == 0) s_req = 0;
+        __syncthreads();
+        for (int i = tid; i < m; i += MATCH_THREADS) {
+            const ProjCand c = P.cand[i];
+            const int held = P.cur[i];
+            if (c.lvl < 0 || held == -2 || (held >= 0 && owner[held] == i)) continue;
+            int bestIdx = -1, bestDist = INT_MAX;
+            int cx0, cx1, cy0, cy1;
+            if (grid_window(fc, c.u, c.v, c.r, cx0, cx1, cy0, cy1)) {
+                const uint4* dq = (const uint4*)(P.mp_desc + (size_t)P.points[i] * 32);
+                const uint4 a0 = dq[0], a1 = dq[1];
+                for (int cx = cx0; cx <= cx1; cx++)
+                    for (int cy = cy0; cy <= cy1; cy++) {
+                        const int cell = cx * GRID_ROWS + cy;
+                        for (int a = cell_start[cell], e = cell_start[cell + 1]; a < e; a++) {
+                            const int idx = items[a];
+                            if (owner[idx] <= i) continue;  // vpMatched[idx] set by the entry or an earlier candidate
+                            const gf_keypoint kp = P.kps[idx];
+                            if (!(fabsf(kp.x - c.u) <= c.r && fabsf(kp.y - c.v) <= c.r)) continue;
+                            if (kp.octave < c.lvl - 1 || kp.octave > c.lvl) continue;
+                            const uint4* dk = (const uint4*)(P.desc + (size_t)idx * 32);
+                            const int d = hamming_regs(a0, a1, dk[0], dk[1]);
+                            if (d < bestDist) {
+                                bestDist = d;
+                                bestIdx = idx;
+                            }
+                        }
+                    }
+            }
+            if (bestDist <= SP_TH_LOW) {
+                P.cur[i] = bestIdx;
+                atomicMin(&owner[bestIdx], i);
+                s_req = 1;
+            } else {
+                P.cur[i] = -2;
+            }
+        }
+        __syncthreads();
+        const int req = s_req;
+        __syncthreads();
+        if (!req) break;
+    }
+    int nm = 0;
+    for (int k = tid; k < n; k += MATCH_THREADS) {
+        const int o = owner[k];
+        if (o >= 0 && o < m) {
+            P.matched[k] = P.points[o];
+            nm++;
+        }
+    }
+    if (nm) atomicAdd(&s_nm, nm);
+    __syncthreads();
+    if (tid == 0) *P.nmatches = s_nm;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gf_search_kf_sim3_projection(gf_ctx* ctx, const gf_frame_info* fi, const float Scw[16], const gf_keypoint* kps,
+                                 const uint8_t* desc, int n, const gf_map_point* mps, const uint8_t* mp_desc,
+                                 const uint8_t* mp_bad, int nmp, const int32_t* points, int npoints, int32_t* matched,
+                                 int th, int* nmatches) {
+    GF_CHECK(ctx && fi && Scw && nmatches, GF_ERR_ARG, "gf_search_kf_sim3_projection: null arg");
+    GF_CHECK(fi->nlevels >= 1 && fi->nlevels <= 16, GF_ERR_ARG, "nlevels out of range");
+    GF_CHECK(fi->max_x > fi->min_x && fi->max_y > fi->min_y, GF_ERR_ARG, "empty image bounds");
+    GF_CHECK(n >= 0 && n <= KP_MAX, GF_ERR_UNSUPPORTED, "at most 4096 keyframe keypoints");
+    GF_CHECK(nmp >= 0 && npoints >= 0, GF_ERR_ARG, "negative count");
+    *nmatches = 0;
+    if (n == 0 || npoints == 0) return GF_OK;
+    GF_CHECK(kps && desc && matched && points && mps && mp_desc && nmp > 0, GF_ERR_ARG,
+             "gf_search_kf_sim3_projection: null buffer");
+    for (int i = 0; i < npoints; i++)
+        GF_CHECK(points[i] >= 0 && points[i] < nmp, GF_ERR_ARG, "candidate map point id out of range");
+    for (int i = 0; i < n; i++) GF_CHECK(matched[i] < nmp, GF_ERR_ARG, "matched map point id out of range");
+    GF_HIP(hipSetDevice(ctx->device));
+    size_t off = 0;
+    std::vector<std::pair<const void*, size_t>> parts;
+    auto add = [&](const void* h, size_t bytes) {
+        const size_t o = off;
+        parts.push_back({h, bytes});
+        off += (bytes + 15) & ~(size_t)15;
+        return o;
+    };
+    const size_t o_k = add(kps, sizeof(gf_keypoint) * (size_t)n), o_d = add(desc, 32 * (size_t)n),
+                 o_mp = add(mps, sizeof(gf_map_point) * (size_t)nmp), o_md = add(mp_desc, 32 * (size_t)nmp),
+                 o_bad = add(mp_bad, mp_bad ? (size_t)nmp : 0), o_pts = add(points, 4 * (size_t)npoints),
+                 o_m = add(matched, 4 * (size_t)n), o_mark = add(nullptr, (size_t)nmp),
+                 o_cand = add(nullptr, sizeof(ProjCand) * (size_t)npoints), o_cur = add(nullptr, 4 * (size_t)npoints),
+                 o_nm = add(nullptr, 4);
+    void* dbuf;
+    int rc = gf::ws_get(ctx, 0, off, &dbuf);
+    if (rc) return rc;
+    uint8_t* base = (uint8_t*)dbuf;
+    hipStream_t s = ctx->stream;
+    size_t cur = 0;
+    for (auto& pr : parts) {
+        if (pr.first && pr.second) GF_HIP(hipMemcpyAsync(base + cur, pr.first, pr.second, hipMemcpyHostToDevice, s));
+        cur += (pr.second + 15) & ~(size_t)15;
+    }
+    GF_HIP(hipMemsetAsync(base + o_mark, 0, (size_t)nmp, s));
+    ProjArgs P{};
+    // Decompose Scw (:866-871): scw = sqrt(row0 . row0) (Mat::dot, a double sum),
+    // Rcw = sRcw / scw and tcw = t / scw as one float factor 1 / scw, Ow = -Rcw^T tcw
+    const double d0 = ((double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1]) + (double)Scw[2] * Scw[2];
+    const float scw = (float)std::sqrt(d0);
+    const float inv = (float)(1.0 / (double)scw);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) P.T[4 * r + c] = Scw[4 * r + c] * inv;
+    for (int r = 0; r < 3; r++) P.Ow[r] = -((P.T[r] * P.T[3] + P.T[4 + r] * P.T[7]) + P.T[8 + r] * P.T[11]);
+    P.kps = (const gf_keypoint*)(base + o_k);
+    P.desc = base + o_d;
+    P.n = n;
+    P.mps = (const gf_map_point*)(base + o_mp);
+    P.mp_desc = base + o_md;
+    P.mp_bad = mp_bad ? base + o_bad : nullptr;
+    P.nmp = nmp;
+    P.points = (const int32_t*)(base + o_pts);
+    P.m = npoints;
+    P.matched = (int32_t*)(base + o_m);
+    P.mark = base + o_mark;
+    P.cand = (ProjCand*)(base + o_cand);
+    P.cur = (int32_t*)(base + o_cur);
+    P.th = (float)th;
+    P.nmatches = (int32_t*)(base + o_nm);
+    {
+        GF_PROF(ctx, s, "k_search_proj_sim3");
+        GF_LAUNCH(k_search_proj_sim3, 1, MATCH_THREADS, sizeof(int) * ((size_t)NCELLS + 1 + 3 * (size_t)n), s,
+                  gf::make_frame_const(fi), P);
+        GF_HIP(hipGetLastError());
+    }
+    int32_t nm = 0;
+    GF_HIP(hipMemcpyAsync(matched, base + o_m, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    GF_HIP(hipMemcpyAsync(&nm, base + o_nm, 4, hipMemcpyDeviceToHost, s));
+    GF_HIP(hipStreamSynchronize(s));
+    *nmatches = nm;
+    return GF_OK;
+}
 
 int gf_search_by_sim3(gf_ctx* ctx, const gf_frame_info* fi, const float* Tcw1, const gf_keypoint* kps1,
                       const uint8_t* desc1, int n1, const int32_t* kf_mp1, const float* Tcw2, const gf_keypoint* kps2,

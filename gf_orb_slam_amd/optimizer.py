@@ -86,6 +86,160 @@ class Optimizer:
                                           ctypes.c_float(cx), ctypes.c_float(cy), ptr(d_outlier), ptr(d_ninliers),
                                           ptr(d_iterations), stream if stream is not None else ctx.stream))
 
+    @staticmethod
+    def OptimizeSim3(kf1, kf2, matches1, S12, mp_pos, mp_bad=None, th2=10, ctx=None):
+        """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2)
+        (Optimizer.cc:2019-2215). kf1 / kf2: ``sim3.Sim3KeyFrame``; matches1:
+        per KF1 keypoint the id of the KF2 map point matched to it (-1 = NULL);
+        S12: the estimate, ``(s, R, t)`` as the Sim3Solver hands it over (float;
+        the quaternion is Quaterniond(Matrix3d) of R, as ``g2o::Sim3(R, t, s)``
+        builds it) or the 8 doubles ``qx qy qz qw tx ty tz s`` of a g2o::Sim3;
+        mp_pos: [n_mp, 3] world positions; mp_bad: isBad(). The pair list is
+        the reference's (:2072-2111): pairs with a NULL or bad point or with
+        ``GetIndexInKeyFrame(pKF2) < 0`` are skipped and keep their match.
+        -> (nIn, S12 as 8 doubles, matches1 with the rejected matches cleared)."""
+        from .sim3 import _to_camera
+
+        m1 = np.asarray(matches1, np.int32).copy()
+        mp_pos = np.asarray(mp_pos, np.float32).reshape(-1, 3)
+        bad = np.zeros(len(mp_pos), bool) if mp_bad is None else np.asarray(mp_bad, bool)
+        idx, X1, X2, z1, z2, w1, w2 = [], [], [], [], [], [], []
+        for i in range(len(m1)):
+            mp2 = int(m1[i])
+            if mp2 < 0:
+                continue
+            mp1 = int(kf1.mp_ids[i])
+            i2 = kf2.index_of(mp2)
+            if mp1 < 0 or bad[mp1] or bad[mp2] or i2 < 0:
+                continue
+            idx.append(i)
+            X1.append(_to_camera(kf1.Tcw, mp_pos[mp1]))
+            X2.append(_to_camera(kf2.Tcw, mp_pos[mp2]))
+            z1.append((kf1.kps["x"][i], kf1.kps["y"][i]))
+            z2.append((kf2.kps["x"][i2], kf2.kps["y"][i2]))
+            # invSigma2 of KF1's level; sigma2 of KF2's: GetSigma2 at :2140
+            w1.append(np.float32(1.0) / np.float32(kf1.level_sigma2[kf1.kps["octave"][i]]))
+            w2.append(np.float32(kf2.level_sigma2[kf2.kps["octave"][i2]]))
+        nin, S, inl, _ = Optimizer.optimize_sim3_pairs(X1, X2, z1, z2, w1, w2, kf1.K, kf2.K, S12, th2, ctx)
+        m1[np.asarray(idx, np.int64)[~inl.astype(bool)]] = -1
+        return nin, S, m1
+
+    @staticmethod
+    def optimize_sim3_pairs(X1, X2, z1, z2, w1, w2, K1, K2, S12, th2=10, ctx=None):
+        """Raw pair-list form of OptimizeSim3 over ``gf_optimize_sim3`` (see
+        abi.h for the arrays). -> (nIn, S12 as 8 doubles, inlier[n], stats[4] =
+        iterations of the two rounds, LM trials of the two)."""
+        ctx = ctx or default_context()
+        c = lambda a, k: np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, k))  # noqa: E731
+        X1, X2, z1, z2 = c(X1, 3), c(X2, 3), c(z1, 2), c(z2, 2)
+        w1, w2 = np.ascontiguousarray(w1, np.float32).reshape(-1), np.ascontiguousarray(w2, np.float32).reshape(-1)
+        n = len(X1)
+        assert len(X2) == len(z1) == len(z2) == len(w1) == len(w2) == n
+        S = sim3_to_g2o(S12)
+        inl = np.zeros(max(n, 1), np.uint8)
+        nin = ctypes.c_int32()
+        stats = np.zeros(4, np.int32)
+        # held in names: a temporary would be freed before the call reads it
+        k1 = np.ascontiguousarray(K1, np.float32).reshape(4)
+        k2 = np.ascontiguousarray(K2, np.float32).reshape(4)
+        p = (lambda a: ptr(a) if n else None)
+        check(lib().gf_optimize_sim3(ctx.handle, n, p(X1), p(X2), p(z1), p(z2), p(w1), p(w2), ptr(k1), ptr(k2),
+                                     ctypes.c_float(th2), ptr(S), p(inl), ctypes.byref(nin), ptr(stats)))
+        return int(nin.value), S, inl[:n].copy(), stats
+
+    @staticmethod
+    def optimize_sim3_batch_dev(d_X1, d_X2, d_z1, d_z2, d_w1, d_w2, d_offsets, d_K, d_th2, d_S12, d_inlier, d_nin,
+                                d_stats=None, ctx=None, stream=None) -> None:
+        """Ragged batched device form (``gf_optimize_sim3_dev``): torch tensors
+        (or raw pointers) already on the GPU; problem p's pairs are rows
+        [d_offsets[p], d_offsets[p + 1])."""
+        ctx = ctx or default_context()
+        nprob = (int(d_nin.numel()) if hasattr(d_nin, "numel") else int(len(d_nin)))
+        check(lib().gf_optimize_sim3_dev(ctx.handle, nprob, ptr(d_X1), ptr(d_X2), ptr(d_z1), ptr(d_z2), ptr(d_w1),
+                                         ptr(d_w2), ptr(d_offsets), ptr(d_K), ptr(d_th2), ptr(d_S12), ptr(d_inlier),
+                                         ptr(d_nin), ptr(d_stats), stream if stream is not None else ctx.stream))
+
+
+def quat_from_R(R) -> np.ndarray:
+    """Eigen's Quaterniond(Matrix3d) (the trace-branch algorithm, no
+    normalisation) of a rotation given in any float type -> (x, y, z, w)."""
+    m = np.asarray(R, np.float64).reshape(3, 3)
+    t = m[0, 0] + (m[1, 1] + m[2, 2])
+    q = np.zeros(4, np.float64)
+    if t > 0:
+        t = np.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[0] = (m[2, 1] - m[1, 2]) * t
+        q[1] = (m[0, 2] - m[2, 0]) * t
+        q[2] = (m[1, 0] - m[0, 1]) * t
+    else:
+        i = 0
+        if m[1, 1] > m[0, 0]:
+            i = 1
+        if m[2, 2] > m[i, i]:
+            i = 2
+        j = (i + 1) % 3
+        k = (j + 1) % 3
+        t = np.sqrt(m[i, i] - m[j, j] - m[k, k] + 1.0)
+        q[i] = 0.5 * t
+        t = 0.5 / t
+        q[3] = (m[k, j] - m[j, k]) * t
+        q[j] = (m[j, i] + m[i, j]) * t
+        q[k] = (m[k, i] + m[i, k]) * t
+    return q
+
+
+def sim3_to_g2o(S12) -> np.ndarray:
+    """``(s, R, t)`` (g2o::Sim3(Matrix3d, Vector3d, double) of the float values)
+    or 8 doubles -> qx qy qz qw tx ty tz s as a fresh float64 array."""
+    if isinstance(S12, (tuple, list)) and len(S12) == 3:
+        s, R, t = S12
+        out = np.zeros(8, np.float64)
+        out[:4] = quat_from_R(np.asarray(R, np.float32))
+        out[4:7] = np.asarray(t, np.float32).reshape(3).astype(np.float64)
+        out[7] = np.float64(np.float32(s))
+        return out
+    return np.ascontiguousarray(S12, np.float64).reshape(8).copy()
+
+
+def _quat_rotate(q, v):
+    """Eigen's quaternion * vector: v + w*uv + q x uv with uv = 2 (q x v)."""
+    x, y, z, w = (float(c) for c in q)
+    uv = [y * v[2] - z * v[1], z * v[0] - x * v[2], x * v[1] - y * v[0]]
+    uv = [u + u for u in uv]
+    c = [y * uv[2] - z * uv[1], z * uv[0] - x * uv[2], x * uv[1] - y * uv[0]]
+    return [v[0] + w * uv[0] + c[0], v[1] + w * uv[1] + c[1], v[2] + w * uv[2] + c[2]]
+
+
+def sim3_mul(A, B) -> np.ndarray:
+    """g2o::Sim3::operator* (sim3.h:266-272) on two 8-double similarities."""
+    ax, ay, az, aw = (float(c) for c in A[:4])
+    bx, by, bz, bw = (float(c) for c in B[:4])
+    out = np.zeros(8, np.float64)
+    out[0] = aw * bx + ax * bw + ay * bz - az * by
+    out[1] = aw * by + ay * bw + az * bx - ax * bz
+    out[2] = aw * bz + az * bw + ax * by - ay * bx
+    out[3] = aw * bw - ax * bx - ay * by - az * bz
+    rt = _quat_rotate(A[:4], [float(c) for c in B[4:7]])
+    s = float(A[7])
+    for i in range(3):
+        out[4 + i] = s * rt[i] + float(A[4 + i])
+    out[7] = s * float(B[7])
+    return out
+
+
+def sim3_from_g2o(S) -> tuple:
+    """8 doubles -> (s, R [3, 3], t [3]) in double: Quaterniond::toRotationMatrix."""
+    x, y, z, w = (float(v) for v in S[:4])
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    R = np.array([[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx],
+                  [txz - twy, tyz + twx, 1 - (txx + tyy)]], np.float64)
+    return float(S[7]), R, np.asarray(S[4:7], np.float64).copy()
+
 
 # ---------------------------------------------------------------- local BA (B1)
 BA_LOCAL, BA_LOCAL_FIXED, BA_FIXED = 0, 1, 2

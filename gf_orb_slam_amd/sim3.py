@@ -12,6 +12,12 @@ n_inliers)`` with ``inliers`` indexed by KF1 keypoint like the reference's
 process-wide ``std::rand()`` of the reference is the :class:`Rand` of
 ``pnp.py``, shared by the solvers of one ``ComputeSim3`` round robin
 (LoopClosing.cc:300-352).
+
+``compute_sim3`` is that round robin up to the first Sim3 a solver returns;
+``compute_sim3_loop`` is the whole of ``ComputeSim3`` (:261-408): it decides
+each candidate with ``Optimizer.OptimizeSim3`` (``optimizer.py``), searches the
+loop map points with ``search_by_projection_sim3`` (ORBmatcher.cc:855-977) and
+accepts the loop at 40 matches.
 """
 from __future__ import annotations
 
@@ -219,3 +225,115 @@ def compute_sim3(info, current, candidates, mps, mp_desc, rand: Rand, mp_bad=Non
                 res[i].update(T12=T12, s=s, R=Rm, t=t, matches=m, n_inliers=ninl)
                 return res
     return res
+
+
+def search_by_projection_sim3(info, kf, desc, Scw, points, matched, mps, mp_desc, th=10, mp_bad=None, ctx=None):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+    (ORBmatcher.cc:855-977) over ``gf_search_kf_sim3_projection``. kf: the
+    :class:`Sim3KeyFrame` searched (its keypoints; desc its [n, 32]
+    descriptors); Scw: the 4x4 similarity (sR | t); points: vpPoints as map
+    point ids in list order; matched: vpMatched per keypoint (-1 = NULL).
+    -> (matched with the new matches added, nmatches)."""
+    import ctypes
+
+    ctx = ctx or default_context()
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    m = c(matched, np.int32).copy()
+    S = c(Scw, np.float32).reshape(16)
+    kps, d = c(kf.kps, kf.kps.dtype), c(desc, np.uint8)
+    pts = c(points, np.int32).reshape(-1)
+    mp, md = c(mps, mps.dtype), c(mp_desc, np.uint8)
+    bad = None if mp_bad is None else c(np.asarray(mp_bad).astype(np.uint8), np.uint8)
+    nm = ctypes.c_int(0)
+    check(lib().gf_search_kf_sim3_projection(ctx.handle, ctypes.byref(info), ptr(S), ptr(kps), ptr(d), len(kps),
+                                             ptr(mp), ptr(md), ptr(bad), len(mp), ptr(pts) if len(pts) else None,
+                                             len(pts), ptr(m), int(th), ctypes.byref(nm)))
+    return m, int(nm.value)
+
+
+def loop_map_points(kfs, mp_bad=None):
+    """mvpLoopMapPoints (LoopClosing.cc:363-382): the map points of the given
+    keyframes (the matched keyframe's covisibles, then the matched keyframe),
+    slot order, NULL and bad ones skipped, each point once at its first
+    occurrence (mnLoopPointForKF)."""
+    seen, out = set(), []
+    for kf in kfs:
+        for mp in np.asarray(kf.mp_ids):
+            mp = int(mp)
+            if mp < 0 or (mp_bad is not None and mp_bad[mp]) or mp in seen:
+                continue
+            seen.add(mp)
+            out.append(mp)
+    return np.asarray(out, np.int32)
+
+
+def compute_sim3_loop(info, current, candidates, mps, mp_desc, rand: Rand, covisibles=None, mp_bad=None, ctx=None):
+    """The whole of LoopClosing::ComputeSim3 (LoopClosing.cc:261-408). As
+    :func:`compute_sim3` up to the first Sim3 a solver returns; then, as the
+    reference does (:332-349), SearchBySim3(..., 7.5) and
+    Optimizer::OptimizeSim3(current, candidate, matches, gScm, 10): fewer than
+    20 inliers send the round robin on to the next solver, 20 or more accept
+    the candidate with Scw = Scm * Smw. covisibles[i]: the
+    :class:`Sim3KeyFrame` list GetVectorCovisibleKeyFrames() of candidate i
+    returns (default none). The loop map points of those and of the matched
+    keyframe go through SearchByProjection(current, Scw, ..., 10), and the loop
+    is accepted when at least 40 of the current keyframe's keypoints are
+    matched. -> dict: ``accepted``, ``matched`` (candidate index or None),
+    ``Scw`` (4x4 float32), ``gScw`` (8 doubles), ``gScm``, ``matches`` (per
+    current keypoint, -1 = NULL), ``n_total``, ``candidates`` (one dict each:
+    ``discarded``, ``n_opt`` = the OptimizeSim3 results in call order)."""
+    from .bow import search_by_bow
+    from .optimizer import Optimizer, sim3_from_g2o, sim3_mul, sim3_to_g2o
+
+    ctx = ctx or default_context()
+    kf_c, desc_c, fv_c = current
+    res = [dict(discarded=None, n_opt=[]) for _ in candidates]
+    out = dict(accepted=False, matched=None, Scw=None, gScw=None, gScm=None, matches=None, n_total=0, candidates=res)
+    solvers, bow = {}, {}
+    for i, (kf, desc, fv) in enumerate(candidates):
+        nm, m12 = search_by_bow(1, 0.75, True, (fv_c, desc_c, kf_c.kps, kf_c.mp_ids), (fv, desc, kf.kps, kf.mp_ids),
+                                ctx)
+        if nm < 20:
+            res[i]["discarded"] = "few_matches"
+            continue
+        bow[i] = m12
+        solvers[i] = Sim3Solver(kf_c, kf, m12, mps["pos"], mp_bad, ctx)
+        solvers[i].set_ransac_parameters(0.99, 20, 300)
+    active = len(solvers)
+    while active > 0 and out["matched"] is None:
+        for i in sorted(solvers):
+            if res[i]["discarded"]:
+                continue
+            T12, no_more, vb, _ = solvers[i].iterate(5, rand)
+            if no_more:
+                res[i]["discarded"] = "no_more"
+                active -= 1
+            if T12 is None:
+                continue
+            kf, desc, _ = candidates[i]
+            s, Rm, t = solvers[i].estimated_scale(), solvers[i].estimated_rotation(), \
+                solvers[i].estimated_translation()
+            m = np.where(vb, bow[i], -1).astype(np.int32)
+            m, _ = search_by_sim3(info, kf_c, desc_c, kf, desc, mps, mp_desc, m, s, Rm, t, 7.5, mp_bad, ctx)
+            nin, gScm, m = Optimizer.OptimizeSim3(kf_c, kf, m, (s, Rm, t), mps["pos"], mp_bad, 10, ctx)
+            res[i]["n_opt"].append(nin)
+            if nin >= 20:
+                # gSmw from the candidate's pose with scale 1 (:343), mg2oScw = gScm * gSmw
+                Tmw = np.asarray(kf.Tcw, np.float32).reshape(4, 4)
+                gScw = sim3_mul(gScm, sim3_to_g2o((1.0, Tmw[:3, :3], Tmw[:3, 3])))
+                sw, Rw, tw = sim3_from_g2o(gScw)
+                Scw = np.eye(4, dtype=np.float32)  # Converter::toCvMat(g2o::Sim3): s*R | t cast to float
+                Scw[:3, :3] = (sw * Rw).astype(np.float32)
+                Scw[:3, 3] = tw.astype(np.float32)
+                out.update(matched=i, Scw=Scw, gScw=gScw, gScm=gScm, matches=m)
+                break
+    if out["matched"] is None:
+        return out
+    i = out["matched"]
+    kfs = list(covisibles[i]) if covisibles is not None else []
+    pts = loop_map_points(kfs + [candidates[i][0]], mp_bad)
+    m, _ = search_by_projection_sim3(info, kf_c, desc_c, out["Scw"], pts, out["matches"], mps, mp_desc, 10, mp_bad, ctx)
+    out["matches"] = m
+    out["n_total"] = int((m >= 0).sum())
+    out["accepted"] = out["n_total"] >= 40
+    return out

@@ -818,6 +818,62 @@ int gf_search_by_sim3(gf_ctx* ctx, const gf_frame_info* fi, const float* Tcw1, c
                       const uint8_t* desc2, int n2, const int32_t* kf_mp2, const gf_map_point* mps,
                       const uint8_t* mp_desc, const uint8_t* mp_bad, int nmp, int32_t* matches12, float s12,
                       const float R12[9], const float t12[3], float th, int* nfound);
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2)
+ * (src/Optimizer.cc:2019-2215) for one keyframe pair, host arrays. A problem
+ * is the routine's edge list after its own filtering (:2072-2111), in that
+ * order, n pairs: X1 / X2 (n x 3) the matched map points in camera 1 / camera
+ * 2 coordinates (Rcw*Xw + tcw in float), z1 / z2 (n x 2) the undistorted
+ * keypoints of KF1 / KF2, w1 the information of EdgeSim3ProjectXYZ =
+ * KF1's invSigma2[octave1], w2 the information of EdgeInverseSim3ProjectXYZ =
+ * KF2's sigma2[octave2]: the reference calls GetSigma2, not GetInvSigma2, at
+ * :2140, and that is kept. K1, K2 = (fx, fy, cx, cy). deltaHuber = sqrt(th2)
+ * is taken in float (:2068). S12 (in and out) is the g2o::Sim3 estimate in the
+ * order of its operator[]: qx qy qz qw tx ty tz s, in double; the quaternion
+ * is Quaterniond(Matrix3d) of the solver's rotation and is not normalised by
+ * any g2o::Sim3 operation. The Jacobians are BaseBinaryEdge's central
+ * differences (core/base_binary_edge.hpp:147-196), the LM is the reference's
+ * modified OptimizationAlgorithmLevenberg::solve
+ * (core/optimization_algorithm_levenberg.cpp:61-164), the linear solve a 7x7
+ * Eigen::LDLT. optimize(5); pairs with chi2(e12) > th2 || chi2(e21) > th2 are
+ * dropped; with fewer than 10 left the routine returns 0 and S12 stays as it
+ * came in; else optimize(nBad > 0 ? 10 : 5) and the same test again. The chi2
+ * tested are those of the last LM trial evaluated (no computeError() before
+ * chi2()), the rejected estimate's when that trial was popped. Outputs: inlier
+ * (n bytes: 1 = vpMatches1 entry kept, 0 = cleared), nin (the return value),
+ * stats (4 ints or NULL: iterations of the two rounds, LM trials of the two). */
+int gf_optimize_sim3(gf_ctx* ctx, int n, const float* X1, const float* X2, const float* z1, const float* z2,
+                     const float* w1, const float* w2, const float K1[4], const float K2[4], float th2, double S12[8],
+                     uint8_t* inlier, int32_t* nin, int32_t* stats);
+/* Device batch of Optimizer::OptimizeSim3 (src/Optimizer.cc:2019-2215), ragged:
+ * problem p's pairs are rows [d_offsets[p], d_offsets[p + 1]) of the pair
+ * arrays and of d_inlier; d_K is [nprob][8] (K1 then K2), d_th2 [nprob],
+ * d_S12 [nprob][8] in and out, d_nin [nprob], d_stats [nprob][4] or NULL. One
+ * wave per problem. Asynchronous on `stream`. Preconditions, as for the other
+ * _dev entries: the buffers and `stream` belong to ctx's device, which is the
+ * caller's current one; d_offsets is non-decreasing with d_offsets[0] >= 0 and
+ * d_offsets[nprob] within the pair arrays. The offsets live on the device and
+ * are not read back: a decreasing step is run as an empty problem, nothing
+ * else is checked. */
+int gf_optimize_sim3_dev(gf_ctx* ctx, int nprob, const float* d_X1, const float* d_X2, const float* d_z1,
+                         const float* d_z2, const float* d_w1, const float* d_w2, const int32_t* d_offsets,
+                         const float* d_K, const float* d_th2, double* d_S12, uint8_t* d_inlier, int32_t* d_nin,
+                         int32_t* d_stats, void* stream);
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+ * (src/ORBmatcher.cc:855-977), the search LoopClosing::ComputeSim3 runs over
+ * the loop map points once a candidate is accepted (LoopClosing.cc:385), host
+ * arrays. Scw is the row-major 4x4 similarity (sR | t), decomposed as at
+ * :866-871. kps / desc (n <= 4096) are the keyframe's undistorted keypoints
+ * and descriptors; points (npoints map point ids into mps / mp_desc / mp_bad)
+ * is vpPoints in list order; matched (n, in and out) is vpMatched as map point
+ * ids, -1 = NULL. Points named in matched at entry are skipped (the set is
+ * built once, :874). vpMatched[bestIdx] is written inside the candidate loop,
+ * so a keypoint taken by an earlier candidate is gone for the later ones: the
+ * result equals the serial list-order result. KeyFrame::GetFeaturesInArea
+ * order decides ties. nmatches: matches added. */
+int gf_search_kf_sim3_projection(gf_ctx* ctx, const gf_frame_info* fi, const float Scw[16], const gf_keypoint* kps,
+                                 const uint8_t* desc, int n, const gf_map_point* mps, const uint8_t* mp_desc,
+                                 const uint8_t* mp_bad, int nmp, const int32_t* points, int npoints, int32_t* matched,
+                                 int th, int* nmatches);
 
 /* ------------------------------------------------ monocular initialisation
  * ORB_SLAM::Initializer (src/Initializer.cc, include/Initializer.h):
