@@ -64,6 +64,13 @@ all: $(SIM3OPTREF)
 $(SIM3OPTREF): tests/helpers/sim3opt_ref.cpp include/gfslam/abi.h
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of OptimizeEssentialGraph
+# (tests/test_essgraph_cpu.py, tests/test_essgraph_gpu.py), same flags
+ESSGRAPHREF = tests/helpers/libessgraphref.so
+all: $(ESSGRAPHREF)
+$(ESSGRAPHREF): tests/helpers/essgraph_ref.cpp include/gfslam/abi.h
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

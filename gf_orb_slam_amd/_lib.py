@@ -34,6 +34,33 @@ class KeyPoint(ctypes.Structure):
                 ("octave", ctypes.c_int32), ("class_id", ctypes.c_int32)]
 
 
+class EssGraphProblem(ctypes.Structure):
+    """gf_essgraph_problem."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("nkf", "npts", "ncorr", "nlc", "loop_kf", "cur_kf")] + [
+        (n, ctypes.c_void_p) for n in ("kf_id", "kf_Tcw", "parent", "cov_start", "cov_nbr", "cov_weight", "le_start",
+                                       "le_nbr", "lc_key", "lc_start", "lc_nbr", "corr_idx", "corrected",
+                                       "noncorrected", "pt_pos", "pt_bad", "pt_ref", "pt_corrected_ref")]
+
+
+class EssGraphStats(ctypes.Structure):
+    """gf_essgraph_stats."""
+
+    _fields_ = [("iterations", ctypes.c_int32), ("trials", ctypes.c_int32), ("stop", ctypes.c_int32),
+                ("ntrace", ctypes.c_int32), ("chi2_initial", ctypes.c_double), ("chi2_final", ctypes.c_double)]
+
+
+class EssGraphResult(ctypes.Structure):
+    """gf_essgraph_result."""
+
+    _fields_ = [("kf_Tcw", ctypes.c_void_p), ("pt_pos", ctypes.c_void_p), ("stats", EssGraphStats),
+                ("trace_lambda", ctypes.c_void_p), ("trace_chi2", ctypes.c_void_p),
+                ("trace_accepted", ctypes.c_void_p)]
+
+
+ESSGRAPH_MAX_KF = 4096
+ESSGRAPH_TRACE = 200
+
 _lib = None
 
 
@@ -137,6 +164,13 @@ _PROTOS = {
     "gf_optimize_sim3": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P],
     "gf_optimize_sim3_dev": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "gf_search_kf_sim3_projection": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P],
+    "gf_essgraph_plan_create": [_P, _I, _P, _P],
+    "gf_essgraph_plan_edges": [_P, _I, _P, _I, _P],
+    "gf_essgraph_plan_solve": [_P, _P],
+    "gf_essgraph_plan_results": [_P, _P],
+    "gf_essgraph_plan_destroy": [_P],
+    "gf_optimize_essential_graph": [_P, _P, _P],
+    "gf_correct_loop_points": [_P, _I, _P, _P, _P, _I, _P, _P, _P],
     "gf_local_ba": [_P, _P, _P],
     "gf_ba_plan_create": [_P, _I, _P, _P],
     "gf_ba_plan_solve": [_P, _P, _P],

@@ -159,6 +159,20 @@ class Optimizer:
                                          ptr(d_w2), ptr(d_offsets), ptr(d_K), ptr(d_th2), ptr(d_S12), ptr(d_inlier),
                                          ptr(d_nin), ptr(d_stats), stream if stream is not None else ctx.stream))
 
+    @staticmethod
+    def OptimizeEssentialGraph(map, loop_kf, cur_kf, Scurw, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+                               ctx=None) -> dict:
+        """Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, Scurw,
+        NonCorrectedSim3, CorrectedSim3, LoopConnections) (Optimizer.cc:1768-2017)
+        on the GPU (csrc/essgraph.hip). Arguments keep the reference's meaning
+        (``EssGraphArrays`` for the containers; Scurw is unused, as in the
+        reference). -> dict: Tcw [N, 4, 4], pos [M, 3], iterations, trials,
+        stop, chi2_initial, chi2_final and the trial trace."""
+        ctx = ctx or default_context()
+        arr = EssGraphArrays(map, loop_kf, cur_kf, NonCorrectedSim3, CorrectedSim3, LoopConnections)
+        check(lib().gf_optimize_essential_graph(ctx.handle, ctypes.byref(arr.problem), ctypes.byref(arr.result)))
+        return arr.out()
+
 
 def quat_from_R(R) -> np.ndarray:
     """Eigen's Quaterniond(Matrix3d) (the trace-branch algorithm, no
@@ -329,3 +343,145 @@ class LocalBAPlan:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------- essential graph (loop correction)
+class EssGraphArrays:
+    """One map as ``gf_essgraph_problem`` (include/gfslam/abi.h), its numpy
+    arrays kept alive next to the ctypes view, and the result buffers.
+
+    ``map``: dict with kf_id [N], Tcw [N, 4, 4], parent [N] (-1 = none), cov
+    (per keyframe a pair (neighbours, weights) in mvpOrderedConnectedKeyFrames
+    order), loop_edges (per keyframe the GetLoopEdges() indices), pos [M, 3],
+    bad [M], ref [M], corrected_ref [M]. NonCorrectedSim3 / CorrectedSim3:
+    dicts keyframe index -> 8 doubles (qx qy qz qw tx ty tz s) over the same
+    keys; LoopConnections: dict keyframe index -> iterable of indices."""
+
+    def __init__(self, map, loop_kf, cur_kf, NonCorrectedSim3, CorrectedSim3, LoopConnections):
+        from ._lib import ESSGRAPH_TRACE, EssGraphProblem, EssGraphResult
+
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1), np.int32)  # noqa: E731
+        N = len(map["kf_id"])
+
+        def csr(rows):
+            start = np.zeros(len(rows) + 1, np.int32)
+            start[1:] = np.cumsum([len(r) for r in rows])
+            flat = [v for r in rows for v in r]
+            return start, i32(flat)
+
+        assert sorted(CorrectedSim3) == sorted(NonCorrectedSim3), "CorrectedSim3 / NonCorrectedSim3 keys differ"
+        keys = sorted(CorrectedSim3)
+        lck = sorted(LoopConnections)
+        a = {}
+        a["kf_id"] = i32(map["kf_id"])
+        a["kf_Tcw"] = np.ascontiguousarray(map["Tcw"], np.float32).reshape(N, 16)
+        a["parent"] = i32(map["parent"])
+        a["cov_start"], a["cov_nbr"] = csr([list(c[0]) for c in map["cov"]])
+        a["cov_weight"] = i32([w for c in map["cov"] for w in c[1]])
+        a["le_start"], a["le_nbr"] = csr([list(r) for r in map["loop_edges"]])
+        a["lc_key"] = i32(lck)
+        a["lc_start"], a["lc_nbr"] = csr([list(LoopConnections[k]) for k in lck])
+        a["corr_idx"] = i32(keys)
+        a["corrected"] = np.ascontiguousarray([CorrectedSim3[k] for k in keys], np.float64).reshape(-1, 8)
+        a["noncorrected"] = np.ascontiguousarray([NonCorrectedSim3[k] for k in keys], np.float64).reshape(-1, 8)
+        a["pt_pos"] = np.ascontiguousarray(map["pos"], np.float32).reshape(-1, 3)
+        M = len(a["pt_pos"])
+        a["pt_bad"] = np.ascontiguousarray(np.asarray(map["bad"]).astype(np.uint8)).reshape(-1)
+        a["pt_ref"] = i32(map["ref"])
+        a["pt_corrected_ref"] = i32(map["corrected_ref"])
+        assert len(a["pt_bad"]) == len(a["pt_ref"]) == len(a["pt_corrected_ref"]) == M
+        self.a, self.N, self.M = a, N, M
+        order = ("kf_id", "kf_Tcw", "parent", "cov_start", "cov_nbr", "cov_weight", "le_start", "le_nbr", "lc_key",
+                 "lc_start", "lc_nbr", "corr_idx", "corrected", "noncorrected", "pt_pos", "pt_bad", "pt_ref",
+                 "pt_corrected_ref")
+        self.problem = EssGraphProblem(N, M, len(keys), len(lck), int(loop_kf), int(cur_kf),
+                                       *[a[k].ctypes.data if a[k].size else None for k in order])
+        self.Tcw = np.zeros((N, 4, 4), np.float32)
+        self.pos = np.zeros((M, 3), np.float32)
+        self.trace_lambda = np.zeros(ESSGRAPH_TRACE, np.float64)
+        self.trace_chi2 = np.zeros(ESSGRAPH_TRACE, np.float64)
+        self.trace_accepted = np.zeros(ESSGRAPH_TRACE, np.uint8)
+        self.result = EssGraphResult()
+        self.result.kf_Tcw = self.Tcw.ctypes.data
+        self.result.pt_pos = self.pos.ctypes.data if M else None
+        self.result.trace_lambda = self.trace_lambda.ctypes.data
+        self.result.trace_chi2 = self.trace_chi2.ctypes.data
+        self.result.trace_accepted = self.trace_accepted.ctypes.data
+
+    def out(self, stats=None) -> dict:
+        st = stats if stats is not None else self.result.stats
+        n = int(st.ntrace)
+        return dict(Tcw=self.Tcw.copy(), pos=self.pos.copy(), iterations=int(st.iterations), trials=int(st.trials),
+                    stop=int(st.stop), chi2_initial=float(st.chi2_initial), chi2_final=float(st.chi2_final),
+                    trace_lambda=self.trace_lambda[:n].copy(), trace_chi2=self.trace_chi2[:n].copy(),
+                    trace_accepted=self.trace_accepted[:n].astype(bool))
+
+
+class EssentialGraphPlan:
+    """A ragged batch of maps (gf_essgraph_plan_*). ``problems``: a list of
+    argument tuples (map, loop_kf, cur_kf, NonCorrectedSim3, CorrectedSim3,
+    LoopConnections)."""
+
+    def __init__(self, problems: list, ctx=None):
+        from ._lib import EssGraphProblem
+
+        self.ctx = ctx or default_context()
+        self.arrs = [p if isinstance(p, EssGraphArrays) else EssGraphArrays(*p) for p in problems]
+        ps = (EssGraphProblem * len(self.arrs))(*[a.problem for a in self.arrs])
+        self.handle = ctypes.c_void_p()
+        check(lib().gf_essgraph_plan_create(self.ctx.handle, len(self.arrs), ps, ctypes.byref(self.handle)))
+
+    def edges(self, p: int) -> np.ndarray:
+        """The edge rows (i, j, kind) of problem p."""
+        n = ctypes.c_int()
+        check(lib().gf_essgraph_plan_edges(self.handle, p, None, 0, ctypes.byref(n)))
+        rows = np.zeros((max(n.value, 1), 3), np.int32)
+        check(lib().gf_essgraph_plan_edges(self.handle, p, ptr(rows), n.value, ctypes.byref(n)))
+        return rows[:n.value].copy()
+
+    def solve(self, stream=None) -> None:
+        check(lib().gf_essgraph_plan_solve(self.handle, stream if stream is not None else self.ctx.stream))
+
+    def results(self) -> list:
+        from ._lib import EssGraphResult
+
+        rs = (EssGraphResult * len(self.arrs))(*[a.result for a in self.arrs])
+        check(lib().gf_essgraph_plan_results(self.handle, rs))
+        return [a.out(r.stats) for a, r in zip(self.arrs, rs)]
+
+    def close(self) -> None:
+        if self.handle:
+            lib().gf_essgraph_plan_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def optimize_essential_graph_batch(problems: list, ctx=None) -> list:
+    """OptimizeEssentialGraph over a list of maps -> one result dict per map."""
+    plan = EssentialGraphPlan(problems, ctx)
+    try:
+        plan.solve()
+        return plan.results()
+    finally:
+        plan.close()
+
+
+def correct_loop_points(pos, bad, sel, Sfrom, Sto, ctx=None) -> np.ndarray:
+    """``gf_correct_loop_points``: point m with sel[m] = c >= 0 becomes
+    Sto[c].inverse().map(Sfrom[c].map(pos[m])) (LoopClosing.cc:462-491)."""
+    ctx = ctx or default_context()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    bad = np.ascontiguousarray(np.asarray(bad).astype(np.uint8)).reshape(-1)
+    sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+    a = np.ascontiguousarray(Sfrom, np.float64).reshape(-1, 8)
+    b = np.ascontiguousarray(Sto, np.float64).reshape(-1, 8)
+    assert len(bad) == len(sel) == len(pos) and len(a) == len(b)
+    out = np.zeros_like(pos)
+    p = (lambda x: ptr(x) if x.size else None)
+    check(lib().gf_correct_loop_points(ctx.handle, len(pos), p(pos), p(bad), p(sel), len(a), p(a), p(b), p(out)))
+    return out

@@ -337,3 +337,68 @@ def compute_sim3_loop(info, current, candidates, mps, mp_desc, rand: Rand, covis
     out["n_total"] = int((m >= 0).sum())
     out["accepted"] = out["n_total"] >= 40
     return out
+
+
+def sim3_of_pose(T) -> np.ndarray:
+    """g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), 1.0) of a
+    float 4x4 pose (LoopClosing.cc:446-448, :454-456) -> 8 doubles."""
+    from .optimizer import quat_from_R
+
+    T = np.asarray(T, np.float32).reshape(4, 4)
+    S = np.zeros(8, np.float64)
+    S[:4] = quat_from_R(T[:3, :3])
+    S[4:7] = T[:3, 3].astype(np.float64)
+    S[7] = 1.0
+    return S
+
+
+def propagate_loop_correction(Tcw, cur_kf, covisibles, Scw, observations, pos, bad, ctx=None) -> dict:
+    """LoopClosing::CorrectLoop's Sim3 propagation (LoopClosing.cc:428-506)
+    without the UpdateConnections calls.
+
+    Tcw [N, 4, 4]: the keyframe poses; cur_kf: mpCurrentKF; covisibles:
+    mpCurrentKF->GetVectorCovisibleKeyFrames() as indices; Scw: mg2oScw (8
+    doubles, from ``compute_sim3_loop``); observations: per keyframe index its
+    GetMapPointMatches() as map point indices (-1 = NULL; only the corrected
+    keyframes are read); pos [M, 3] / bad [M]: the map points.
+
+    Builds NonCorrectedSim3 (``Sim3(Riw, tiw, 1)``) and CorrectedSim3
+    (``g2oSic * mg2oScw`` with ``Sic = Tiw * Twc`` at scale 1), corrects every
+    map point once (the first corrected keyframe in id order that observes it;
+    the reference walks the map in pointer order) through
+    ``gf_correct_loop_points``, marks mnCorrectedReference and rewrites the
+    corrected keyframes' poses as [R | t/s]. The result holds the inputs of
+    ``Optimizer.OptimizeEssentialGraph``: NonCorrectedSim3, CorrectedSim3, pos,
+    corrected_ref, Tcw."""
+    from .optimizer import correct_loop_points, sim3_from_g2o, sim3_mul
+
+    Tcw = np.asarray(Tcw, np.float32).reshape(-1, 4, 4)
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    bad = np.asarray(bad).astype(bool).reshape(-1)
+    Scw = np.ascontiguousarray(Scw, np.float64).reshape(8)
+    Tcur = Tcw[cur_kf]
+    Twc = np.eye(4, dtype=np.float32)  # KeyFrame::GetPoseInverse
+    Twc[:3, :3] = Tcur[:3, :3].T
+    Twc[:3, 3] = -(Tcur[:3, :3].T @ Tcur[:3, 3])
+    non, cor = {}, {int(cur_kf): Scw.copy()}
+    for i in [int(k) for k in covisibles] + [int(cur_kf)]:
+        if i != cur_kf:
+            Tic = (Tcw[i] @ Twc).astype(np.float32)
+            cor[i] = sim3_mul(sim3_of_pose(Tic), Scw)
+        non[i] = sim3_of_pose(Tcw[i])
+    keys = sorted(cor)
+    sel = np.full(len(pos), -1, np.int32)
+    for c, k in enumerate(keys):
+        obs = np.asarray(observations[k], np.int64).reshape(-1)
+        obs = obs[obs >= 0]
+        obs = obs[(sel[obs] < 0) & ~bad[obs]]
+        sel[obs] = c
+    new_pos = correct_loop_points(pos, bad, sel, [non[k] for k in keys], [cor[k] for k in keys], ctx)
+    corrected_ref = np.where(sel >= 0, np.asarray(keys, np.int32)[np.maximum(sel, 0)], -1).astype(np.int32)
+    T = Tcw.copy()
+    for k in keys:
+        s, R, t = sim3_from_g2o(cor[k])
+        T[k] = np.eye(4, dtype=np.float32)
+        T[k, :3, :3] = R.astype(np.float32)
+        T[k, :3, 3] = (t * (1.0 / s)).astype(np.float32)
+    return dict(NonCorrectedSim3=non, CorrectedSim3=cor, pos=new_pos, corrected_ref=corrected_ref, Tcw=T)

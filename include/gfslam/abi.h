@@ -875,6 +875,103 @@ int gf_search_kf_sim3_projection(gf_ctx* ctx, const gf_frame_info* fi, const flo
                                  const uint8_t* mp_bad, int nmp, const int32_t* points, int npoints, int32_t* matched,
                                  int th, int* nmatches);
 
+/* ------------------------------------------------ essential graph (loop correction)
+ * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1768-2017), the 7-DoF
+ * pose graph LoopClosing::CorrectLoop runs over every keyframe of the map
+ * (LoopClosing.cc:556), and the point correction of CorrectLoop itself
+ * (LoopClosing.cc:462-491). One problem is one map; every index is a position
+ * in the keyframe list (Map::GetAllKeyFrames(), no bad keyframe), whose mnId
+ * are kf_id, strictly increasing (culled ids are absent).
+ *   covisibility: CSR rows in mvpOrderedConnectedKeyFrames order with their
+ *     weights; GetCovisiblesByWeight(100) is a row's prefix with weight >= 100,
+ *     GetWeight a lookup in the row (absent: 0);
+ *   le_*: GetLoopEdges() as CSR; lc_*: the LoopConnections map, keys lc_key
+ *     (nlc of them) with CSR rows lc_start / lc_nbr;
+ *   corr_idx / corrected / noncorrected: the keys of CorrectedSim3 /
+ *     NonCorrectedSim3 (the same key set) and their g2o::Sim3 as
+ *     qx qy qz qw tx ty tz s in double;
+ *   points: GetWorldPos(), isBad(), the reference keyframe (pt_ref, -1 leaves
+ *     the point as it is) and pt_corrected_ref (>= 0 where mnCorrectedByKF ==
+ *     pCurKF->mnId: mnCorrectedReference, used instead of pt_ref).
+ * The edge set is :1832-1957 with the reference's std::set / std::map
+ * iterations (pointer order) run in keyframe-id order (assumption A24); the
+ * linear solve is a tile Cholesky in place of CHOLMOD (A25). The Levenberg
+ * schedule is optimization_algorithm_levenberg.cpp:61-164 with
+ * setUserLambdaInit(1e-16) and optimize(20); Jacobians are BaseBinaryEdge's
+ * central differences (base_binary_edge.hpp:147-196). Poses are written back
+ * as [R | t/s] (:1965-1983), points as correctedSwr.map(Srw.map(p))
+ * (:1986-2016); MapPoint::UpdateNormalAndDepth is the caller's.
+ * Limits: 2 <= nkf <= GF_ESSGRAPH_MAX_KF; the factor's tile envelope must fit
+ * GF_ESSGRAPH_MAX_TILES 64x64 f64 tiles (GF_ERR_CAP otherwise). */
+#define GF_ESSGRAPH_MAX_KF 4096
+#define GF_ESSGRAPH_MAX_TILES 65536 /* 2 GiB of factor */
+#define GF_ESSGRAPH_TRACE 200
+typedef struct gf_essgraph_problem {
+    int32_t nkf, npts, ncorr, nlc;
+    int32_t loop_kf, cur_kf;          /* pLoopKF (the fixed vertex), pCurKF */
+    const int32_t* kf_id;             /* nkf */
+    const float* kf_Tcw;              /* nkf x 16, row-major GetPose() */
+    const int32_t* parent;            /* nkf, -1 = none */
+    const int32_t* cov_start;         /* nkf + 1 */
+    const int32_t* cov_nbr;
+    const int32_t* cov_weight;
+    const int32_t* le_start;          /* nkf + 1 */
+    const int32_t* le_nbr;
+    const int32_t* lc_key;            /* nlc */
+    const int32_t* lc_start;          /* nlc + 1 */
+    const int32_t* lc_nbr;
+    const int32_t* corr_idx;          /* ncorr */
+    const double* corrected;          /* ncorr x 8 */
+    const double* noncorrected;       /* ncorr x 8 */
+    const float* pt_pos;              /* npts x 3 */
+    const uint8_t* pt_bad;            /* npts */
+    const int32_t* pt_ref;            /* npts */
+    const int32_t* pt_corrected_ref;  /* npts */
+} gf_essgraph_problem;
+
+/* stop: 0 = optimize(20) ran out, 1 = rho == 0, 2 = 10 trials failed, 3 = the
+ * _nBad >= 3 rule (optimization_algorithm_levenberg.cpp:151-161). */
+typedef struct gf_essgraph_stats {
+    int32_t iterations, trials, stop, ntrace;
+    double chi2_initial, chi2_final;
+} gf_essgraph_stats;
+
+typedef struct gf_essgraph_result {
+    float* kf_Tcw;             /* nkf x 16 */
+    float* pt_pos;             /* npts x 3 */
+    gf_essgraph_stats stats;
+    double* trace_lambda;      /* GF_ESSGRAPH_TRACE or NULL: lambda of each trial */
+    double* trace_chi2;        /* GF_ESSGRAPH_TRACE or NULL: tempChi */
+    uint8_t* trace_accepted;   /* GF_ESSGRAPH_TRACE or NULL */
+} gf_essgraph_result;
+
+typedef struct gf_essgraph_plan gf_essgraph_plan;
+
+/* Validates nprob maps (a ragged batch), builds each edge set, Hessian index
+ * (rank by id among the free keyframes, as initializeOptimization gives), the
+ * gather lists of the 7x7 blocks and the tile envelope on the host, and
+ * uploads them. nkf < 2, an unsorted kf_id, an index out of range or nkf above
+ * the cap: GF_ERR_ARG, checked before any device work. */
+int gf_essgraph_plan_create(gf_ctx* ctx, int nprob, const gf_essgraph_problem* probs, gf_essgraph_plan** out);
+/* The edge rows (i, j, kind) of problem p in insertion order (Optimizer.cc:
+ * 1832-1957): vertex 0 = i, vertex 1 = j, kind 0 loop connection, 1 spanning
+ * tree, 2 past loop edge, 3 covisibility. rows NULL: only *nedges. */
+int gf_essgraph_plan_edges(gf_essgraph_plan* plan, int p, int32_t* rows, int cap, int* nedges);
+/* optimize(20) of every problem from its uploaded state (:1959-1962) and the
+ * write-back (:1964-2016), on `stream`; the host reads three scalars back per
+ * Levenberg trial. Solving twice gives identical bytes. */
+int gf_essgraph_plan_solve(gf_essgraph_plan* plan, void* stream);
+int gf_essgraph_plan_results(gf_essgraph_plan* plan, gf_essgraph_result* res);
+int gf_essgraph_plan_destroy(gf_essgraph_plan* plan);
+/* Optimizer::OptimizeEssentialGraph (Optimizer.cc:1768-2017) of one map. */
+int gf_optimize_essential_graph(gf_ctx* ctx, const gf_essgraph_problem* prob, gf_essgraph_result* res);
+/* The point loop of LoopClosing::CorrectLoop (LoopClosing.cc:462-491): point m
+ * with sel[m] = c >= 0 becomes to[c].inverse().map(from[c].map(pos[m])) in
+ * double, stored as float; bad points and sel < 0 are copied through. from /
+ * to: nsim x 8 g2o::Sim3 (NonCorrectedSim3 / CorrectedSim3 rows). */
+int gf_correct_loop_points(gf_ctx* ctx, int npts, const float* pos, const uint8_t* bad, const int32_t* sel, int nsim,
+                           const double* from, const double* to, float* pos_out);
+
 /* ------------------------------------------------ monocular initialisation
  * ORB_SLAM::Initializer (src/Initializer.cc, include/Initializer.h):
  * Initializer(ReferenceFrame, sigma, iterations) + Initialize(CurrentFrame,
