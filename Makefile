@@ -71,6 +71,14 @@ all: $(ESSGRAPHREF)
 $(ESSGRAPHREF): tests/helpers/essgraph_ref.cpp include/gfslam/abi.h
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of Fuse(pKF, Scw, ...), SearchAndFuse and
+# MapPoint::Replace (tests/test_loopfuse_cpu.py, tests/test_loopfuse_gpu.py),
+# same flags
+LOOPFUSEREF = tests/helpers/libloopfuseref.so
+all: $(LOOPFUSEREF)
+$(LOOPFUSEREF): tests/helpers/loopfuse_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

@@ -164,6 +164,8 @@ _PROTOS = {
     "gf_optimize_sim3": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P],
     "gf_optimize_sim3_dev": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "gf_search_kf_sim3_projection": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P],
+    "gf_fuse_sim3": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _F, _P],
+    "gf_fuse_sim3_dev": [_P, _P, _I, _P, _P, _P, _P, _I, _P],
     "gf_essgraph_plan_create": [_P, _I, _P, _P],
     "gf_essgraph_plan_edges": [_P, _I, _P, _I, _P],
     "gf_essgraph_plan_solve": [_P, _P],

@@ -1,0 +1,246 @@
+"""What ``LoopClosing::CorrectLoop`` reads and writes of ``Map`` / ``KeyFrame``
+/ ``MapPoint``, as index arrays.
+
+A keyframe is an index into the lists given at construction, a map point an
+index into ``mps``. The slot tables (``KeyFrame::mvpMapPoints``) and the
+observation maps (``MapPoint::mObservations``) are separate state, as in the
+reference: ``AddObservation`` overwrites, and nothing here assumes that the two
+agree or that a point sits in one slot per keyframe. Pointer-ordered containers
+are walked in keyframe-index order (docs/ORACLE_ASSUMPTIONS.md A26).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .matcher import MAP_POINT_DTYPE
+from .orb import KEYPOINT_DTYPE
+
+
+class LoopMap:
+    def __init__(self, info, kf_kps, kf_desc, kf_mp, mps, mp_desc, mp_bad=None, observations=None, kf_bad=None,
+                 distinctive=None, kf_Tcw=None, ref_kf=None, kf_id=None):
+        """info: the FrameInfo every keyframe shares; kf_kps / kf_desc / kf_mp:
+        per keyframe its undistorted keypoints, [n, 32] descriptors and slot
+        table (map point id per keypoint, -1 = NULL); mps (MAP_POINT_DTYPE),
+        mp_desc [M, 32], mp_bad [M]: the map points; observations: per point a
+        dict keyframe -> slot (default: read off the slot tables, the later
+        slot winning as AddObservation does); kf_bad: KeyFrame::isBad();
+        distinctive(desc, offsets, current) -> (best, rows): the
+        ComputeDistinctiveDescriptors used (default: the device's); kf_Tcw
+        [nkf, 4, 4]: the poses (default identity); ref_kf [M]: mpRefKF per point
+        (default its first observing keyframe, -1 without one); kf_id: mnId
+        per keyframe, strictly increasing (default the index)."""
+        self.info = info
+        self.kf_kps = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k in kf_kps]
+        self.kf_desc = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in kf_desc]
+        self.slots = [np.ascontiguousarray(s, np.int32).copy() for s in kf_mp]
+        self.nkf = len(self.kf_kps)
+        self.kf_bad = np.zeros(self.nkf, bool) if kf_bad is None else np.asarray(kf_bad).astype(bool).copy()
+        self.mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE).copy()
+        self.mp_desc = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32).copy()
+        n = len(self.mps)
+        self.mp_bad = np.zeros(n, bool) if mp_bad is None else np.asarray(mp_bad).astype(bool).copy()
+        # bumped whenever a point's descriptor row really changes: what a search made earlier must be redone for
+        self.desc_epoch = np.zeros(n, np.int64)
+        if observations is None:
+            self.obs = [dict() for _ in range(n)]
+            for k, s in enumerate(self.slots):
+                for idx in np.nonzero(s >= 0)[0]:
+                    self.obs[int(s[idx])][k] = int(idx)
+        else:
+            self.obs = [dict(o) for o in observations]
+        self._distinctive = distinctive
+        self.Tcw = (np.tile(np.eye(4, dtype=np.float32), (self.nkf, 1, 1)) if kf_Tcw is None
+                    else np.ascontiguousarray(kf_Tcw, np.float32).reshape(self.nkf, 4, 4).copy())
+        self.kf_id = np.arange(self.nkf, dtype=np.int32) if kf_id is None else np.asarray(kf_id, np.int32).copy()
+        self.ref_kf = (np.asarray([min(o) if o else -1 for o in self.obs], np.int32).reshape(-1) if ref_kf is None
+                       else np.asarray(ref_kf, np.int32).copy())
+        self.corrected_by = np.full(n, -1, np.int32)   # mnCorrectedByKF (a keyframe index)
+        self.corrected_ref = np.full(n, -1, np.int32)  # mnCorrectedReference
+        # the covisibility graph: mConnectedKeyFrameWeights, the ordered covisibles with their weights,
+        # mpParent / mbFirstConnection and the loop edges
+        self.weights = [dict() for _ in range(self.nkf)]
+        self.ordered = [[] for _ in range(self.nkf)]
+        self.ordered_w = [[] for _ in range(self.nkf)]
+        self.parent = [-1] * self.nkf
+        self.first_connection = [True] * self.nkf
+        self.loop_edges = [[] for _ in range(self.nkf)]
+
+    # ------------------------------------------------------------ MapPoint
+    def is_in_keyframe(self, p: int, kf: int) -> bool:
+        """MapPoint::IsInKeyFrame: by the observation map."""
+        return kf in self.obs[p]
+
+    def add_observation(self, p: int, kf: int, idx: int) -> None:
+        """MapPoint::AddObservation (MapPoint.cc:77-81): overwrites."""
+        self.obs[p][int(kf)] = int(idx)
+
+    def replace(self, a: int, b: int) -> None:
+        """``a->Replace(b)`` (MapPoint.cc:136-170): a turns bad, its
+        observations move to b (or are erased from a keyframe that b already
+        observes), and b's descriptor is recomputed."""
+        a, b = int(a), int(b)
+        if a == b:
+            return
+        obs, self.obs[a] = self.obs[a], {}
+        self.mp_bad[a] = True
+        for kf in sorted(obs):
+            idx = obs[kf]
+            if not self.is_in_keyframe(b, kf):
+                self.slots[kf][idx] = b  # ReplaceMapPointMatch
+                self.add_observation(b, kf, idx)
+            else:
+                self.slots[kf][idx] = -1  # EraseMapPointMatch
+        self.compute_distinctive_descriptors([b])
+
+    def compute_distinctive_descriptors(self, ids) -> None:
+        """MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:197-262) of the
+        given points over ``gf_distinctive_descriptors``: the observations of
+        non-bad keyframes in observation-map order; a bad or observation-less
+        point is left as it is."""
+        ids = [int(p) for p in ids if not self.mp_bad[int(p)] and self.obs[int(p)]]
+        if not ids:
+            return
+        rows, offs = [], [0]
+        for p in ids:
+            for kf in sorted(self.obs[p]):
+                if not self.kf_bad[kf]:
+                    rows.append(self.kf_desc[kf][self.obs[p][kf]])
+            offs.append(len(rows))
+        if not rows:
+            return
+        fn = self._distinctive
+        if fn is None:
+            from .matcher import compute_distinctive_descriptors as fn
+        cur = self.mp_desc[ids]
+        _, out = fn(np.asarray(rows, np.uint8).reshape(-1, 32), np.asarray(offs, np.int32), cur)
+        changed = np.any(out != cur, axis=1)
+        for p, row, ch in zip(ids, out, changed):
+            if ch:
+                self.mp_desc[p] = row
+                self.desc_epoch[p] += 1
+
+    def update_normal_and_depth(self, ids) -> None:
+        """MapPoint::UpdateNormalAndDepth (MapPoint.cc:285-324) of the given
+        points on the host. ``cv::norm`` is a double sum, cast to float; a
+        ``Mat / scalar`` is one float factor ``(float)(1 / scalar)``
+        (docs/ORACLE_ASSUMPTIONS.md A22); the rest is float in the reference's
+        order. A bad point returns as in the reference; one without
+        observations or reference keyframe, where the reference divides by
+        zero, is left as it is."""
+        from .matcher import camera_center
+
+        f32 = np.float32
+        sf, scales = f32(self.info.scale_factor), self.info.scale_factors()
+        nlev = len(scales)
+        centre = {}
+
+        def norm(d):
+            return f32(np.sqrt((np.float64(d[0]) * np.float64(d[0]) + np.float64(d[1]) * np.float64(d[1]))
+                               + np.float64(d[2]) * np.float64(d[2])))
+
+        for p in ids:
+            p = int(p)
+            ref = int(self.ref_kf[p])
+            if self.mp_bad[p] or not self.obs[p] or ref < 0 or not len(self.kf_kps[ref]):
+                continue
+            pos = self.mps["pos"][p].astype(f32)
+            normal = np.zeros(3, f32)
+            for kf in sorted(self.obs[p]):
+                if kf not in centre:
+                    centre[kf] = camera_center(self.Tcw[kf])
+                d = pos - centre[kf]
+                normal = normal + d * f32(1.0 / np.float64(norm(d)))
+            if ref not in centre:
+                centre[ref] = camera_center(self.Tcw[ref])
+            dist = norm(pos - centre[ref])
+            level = int(self.kf_kps[ref]["octave"][self.obs[p].get(ref, 0)])  # observations[pRefKF]: 0 when absent
+            self.mps["min_dist"][p] = ((f32(1.0) / sf) * dist) / scales[level]
+            self.mps["max_dist"][p] = (sf * dist) * scales[nlev - 1 - level]
+            self.mps["normal"][p] = normal * f32(1.0 / len(self.obs[p]))
+
+    # ------------------------------------------------------------ KeyFrame
+    def set_pose(self, kf: int, Tcw) -> None:
+        """KeyFrame::SetPose."""
+        self.Tcw[kf] = np.asarray(Tcw, np.float32).reshape(4, 4)
+
+    def add_loop_edge(self, kf: int, other: int) -> None:
+        """KeyFrame::AddLoopEdge: a set."""
+        if other not in self.loop_edges[kf]:
+            self.loop_edges[kf].append(int(other))
+
+    def to_essgraph_map(self) -> dict:
+        """The map dict ``optimizer.EssGraphArrays`` takes."""
+        return dict(kf_id=self.kf_id.copy(), Tcw=self.Tcw.copy(), parent=list(self.parent),
+                    cov=[(list(o), list(w)) for o, w in zip(self.ordered, self.ordered_w)],
+                    loop_edges=[sorted(e) for e in self.loop_edges], pos=self.mps["pos"].copy(),
+                    bad=self.mp_bad.copy(), ref=self.ref_kf.copy(), corrected_ref=self.corrected_ref.copy())
+
+    def add_map_point(self, kf: int, p: int, idx: int) -> None:
+        """KeyFrame::AddMapPoint."""
+        self.slots[kf][idx] = p
+
+    def get_map_points(self, kf: int) -> set:
+        """KeyFrame::GetMapPoints (KeyFrame.cc:238-251): the non-bad points of
+        the slot table."""
+        s = self.slots[kf]
+        s = s[s >= 0]
+        return set(int(p) for p in s[~self.mp_bad[s]])
+
+    def update_best_covisibles(self, kf: int) -> None:
+        """KeyFrame::UpdateBestCovisibles (KeyFrame.cc:141-160): the ordered
+        list rebuilt from every weight, heaviest first, the higher index first
+        among equals (the sort of (weight, KeyFrame*) pairs, reversed)."""
+        pairs = sorted((w, k) for k, w in self.weights[kf].items())[::-1]
+        self.ordered[kf] = [k for _, k in pairs]
+        self.ordered_w[kf] = [w for w, _ in pairs]
+
+    def add_connection(self, kf: int, other: int, weight: int) -> None:
+        """KeyFrame::AddConnection (KeyFrame.cc:126-139)."""
+        if self.weights[kf].get(other) == weight:
+            return
+        self.weights[kf][other] = weight
+        self.update_best_covisibles(kf)
+
+    def update_connections(self, kf: int) -> None:
+        """KeyFrame::UpdateConnections (KeyFrame.cc:332-421). The weight map
+        receives every counted keyframe; the ordered list those with 15 shared
+        points or more, or the single heaviest one; the others hear of it
+        through AddConnection."""
+        kf = int(kf)
+        counter = {}
+        for p in self.slots[kf]:
+            if p < 0 or self.mp_bad[p]:
+                continue
+            for k in self.obs[int(p)]:
+                if k != kf:
+                    counter[k] = counter.get(k, 0) + 1
+        if not counter:
+            return
+        nmax, kmax, pairs = 0, None, []
+        for k in sorted(counter):
+            if counter[k] > nmax:
+                nmax, kmax = counter[k], k
+            if counter[k] >= 15:
+                pairs.append((counter[k], k))
+                self.add_connection(k, kf, counter[k])
+        if not pairs:
+            pairs.append((nmax, kmax))
+            self.add_connection(kmax, kf, nmax)
+        pairs = sorted(pairs)[::-1]
+        self.weights[kf] = dict(counter)
+        self.ordered[kf] = [k for _, k in pairs]
+        self.ordered_w[kf] = [w for w, _ in pairs]
+        if self.first_connection[kf] and kf != 0:
+            self.parent[kf] = self.ordered[kf][0]
+            self.first_connection[kf] = False
+
+    def get_connected_keyframes(self, kf: int) -> set:
+        """KeyFrame::GetConnectedKeyFrames: every key of the weight map."""
+        return set(self.weights[kf])
+
+    def observation_rows(self) -> np.ndarray:
+        """Every observation as a (point, keyframe, slot) row, point-major,
+        keyframe-index order."""
+        out = [(p, kf, o[kf]) for p, o in enumerate(self.obs) for kf in sorted(o)]
+        return np.asarray(out, np.int32).reshape(-1, 3)

@@ -18,9 +18,15 @@ process-wide ``std::rand()`` of the reference is the :class:`Rand` of
 each candidate with ``Optimizer.OptimizeSim3`` (``optimizer.py``), searches the
 loop map points with ``search_by_projection_sim3`` (ORBmatcher.cc:855-977) and
 accepts the loop at 40 matches.
+
+``correct_loop`` is ``LoopClosing::CorrectLoop`` (:426-560) on a
+``loopmap.LoopMap``: ``propagate_loop_correction``, ``loop_fusion`` (:508-525),
+``search_and_fuse`` (SearchAndFuse, :572-585, over ``gf_fuse_sim3_dev``),
+``loop_connections`` (:533-552) and ``Optimizer.OptimizeEssentialGraph``.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -402,3 +408,229 @@ def propagate_loop_correction(Tcw, cur_kf, covisibles, Scw, observations, pos, b
         T[k, :3, :3] = R.astype(np.float32)
         T[k, :3, 3] = (t * (1.0 / s)).astype(np.float32)
     return dict(NonCorrectedSim3=non, CorrectedSim3=cor, pos=new_pos, corrected_ref=corrected_ref, Tcw=T)
+
+
+FUSE_SIM3_RESULT_DTYPE = np.dtype([("kp", "<i4"), ("dist", "<i4")])
+
+
+class FuseSim3Problem(ctypes.Structure):
+    """gf_fuse_sim3_problem: one (keyframe, candidate list) of gf_fuse_sim3_dev; device pointers."""
+
+    _fields_ = [("Scw", ctypes.c_float * 16), ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p),
+                ("n", ctypes.c_int32), ("kf_mp", ctypes.c_void_p), ("points", ctypes.c_void_p),
+                ("npoints", ctypes.c_int32), ("th", ctypes.c_float), ("res", ctypes.c_void_p)]
+
+    @classmethod
+    def make(cls, Scw, kps, desc, n, kf_mp, points, npoints, th, res):
+        """kps .. res: device tensors (None allowed where the count is 0)."""
+        q = cls()
+        q.Scw[:] = [float(x) for x in np.asarray(Scw, np.float32).reshape(16)]
+        dp = lambda b: None if b is None else b.data_ptr()  # noqa: E731
+        q.kps, q.desc, q.kf_mp, q.points, q.res = dp(kps), dp(desc), dp(kf_mp), dp(points), dp(res)
+        q.n, q.npoints, q.th = int(n), int(npoints), float(th)
+        return q
+
+
+def fuse_sim3(info, kf, desc, Scw, points, kf_mp, mps, mp_desc, mp_bad, th=4, ctx=None):
+    """The search of ORBmatcher::Fuse(pKF, Scw, vpPoints, th)
+    (ORBmatcher.cc:1710-1816) over ``gf_fuse_sim3``. kf: the keyframe's
+    keypoints (KEYPOINT_DTYPE, or a :class:`Sim3KeyFrame`); desc: its [n, 32]
+    descriptors; Scw: the 4x4 similarity (sR | t); points: vpPoints as map point
+    ids in list order; kf_mp: the slot table (-1 = NULL); mps, mp_desc, mp_bad:
+    the map. -> (kp, dist) per candidate: the keypoint it would fuse with and
+    its distance, -1 where it leaves the search."""
+    ctx = ctx or default_context()
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    kps = getattr(kf, "kps", kf)
+    kps, d = c(kps, kps.dtype), c(desc, np.uint8)
+    S = c(Scw, np.float32).reshape(16)
+    pts, slots = c(points, np.int32).reshape(-1), c(kf_mp, np.int32).reshape(-1)
+    mp, md = c(mps, mps.dtype), c(mp_desc, np.uint8)
+    bad = None if mp_bad is None else c(np.asarray(mp_bad).astype(np.uint8), np.uint8)
+    res = np.zeros(max(len(pts), 1), FUSE_SIM3_RESULT_DTYPE)
+    check(lib().gf_fuse_sim3(ctx.handle, ctypes.byref(info), ptr(S), ptr(kps) if len(kps) else None,
+                             ptr(d) if len(kps) else None, len(kps), ptr(slots) if len(kps) else None, ptr(mp),
+                             ptr(md), ptr(bad), len(mp), ptr(pts) if len(pts) else None, len(pts), float(th),
+                             ptr(res)))
+    res = res[:len(pts)]
+    return res["kp"].copy(), res["dist"].copy()
+
+
+def _dirty(map, pts, used_epoch):
+    """The candidates whose descriptor row changed since their search."""
+    return map.desc_epoch[pts] != used_epoch
+
+
+def search_and_fuse(map, CorrectedSim3, loop_points, th=4, ctx=None) -> dict:
+    """LoopClosing::SearchAndFuse (LoopClosing.cc:572-585) on a
+    :class:`~gf_orb_slam_amd.loopmap.LoopMap`. CorrectedSim3: keyframe index ->
+    g2o::Sim3 (8 doubles) or the 4x4 float Scw; loop_points: mvpLoopMapPoints
+    as map point ids.
+
+    One ``gf_fuse_sim3_dev`` launch searches every (keyframe, loop point) pair
+    against the map as it stands. The keyframes are then walked in index order
+    and the candidates in list order on the host, where ORBmatcher.cc:1819-1833
+    runs on the live map. ``MapPoint::Replace`` recomputes the surviving loop
+    point's descriptor, the only input of a search that changes during
+    SearchAndFuse, so before keyframe j those of its candidates whose
+    descriptor changed since the launch are searched again in one small call.
+    -> dict: ``nFused`` (keyframe -> count) and ``actions`` (keyframe -> list of
+    ``(point, kp, "add" | "replace" | "keep", replaced_id)``)."""
+    import torch
+
+    from .optimizer import sim3_from_g2o
+
+    kfs = sorted(int(k) for k in CorrectedSim3)
+    pts = np.ascontiguousarray(loop_points, np.int32).reshape(-1)
+    m = len(pts)
+    Scw = {}
+    for k in kfs:
+        S = np.asarray(CorrectedSim3[k])
+        if S.size == 8:  # Converter::toCvMat(g2o::Sim3): s*R | t cast to float
+            s, R, t = sim3_from_g2o(S.astype(np.float64).reshape(8))
+            M = np.eye(4, dtype=np.float32)
+            M[:3, :3] = (s * R).astype(np.float32)
+            M[:3, 3] = t.astype(np.float32)
+            S = M
+        Scw[k] = np.ascontiguousarray(S, np.float32).reshape(4, 4)
+    out = dict(nFused={k: 0 for k in kfs}, actions={k: [] for k in kfs})
+    if m == 0 or not kfs:
+        return out
+    if pts.min() < 0 or pts.max() >= len(map.mps):
+        raise ValueError("loop point id out of range")
+    if len(np.unique(pts)) != m:
+        raise ValueError("a loop point is listed twice (mvpLoopMapPoints holds each point once, LoopClosing.cc:372-379)")
+    # a candidate that is bad or in a keyframe's slot table now is skipped at that keyframe's turn too
+    # (a bad point stays bad; a point in the table is there or bad later): nothing left, nothing to search
+    good = ~map.mp_bad[pts]
+    if not any((good & ~np.isin(pts, list(map.get_map_points(k)))).any() for k in kfs):
+        return out
+    # the launch: every keyframe against the map as it stands
+    ctx = ctx or default_context()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    d_mps, d_md = t(map.mps.view(np.uint8)), t(map.mp_desc)
+    d_bad, d_pts = t(map.mp_bad.astype(np.uint8)), t(pts)
+    keep, probs, d_res = [d_mps, d_md, d_bad, d_pts], [], []
+    for k in kfs:
+        n = len(map.kf_kps[k])
+        bufs = [t(map.kf_kps[k].view(np.uint8)), t(map.kf_desc[k]), t(map.slots[k])] if n else [None] * 3
+        r = torch.empty(m * 2, dtype=torch.int32, device=dev)
+        keep += bufs
+        d_res.append(r)
+        probs.append(FuseSim3Problem.make(Scw[k], bufs[0], bufs[1], n, bufs[2], d_pts, m, th, r))
+    arr = (FuseSim3Problem * len(probs))(*probs)
+    check(lib().gf_fuse_sim3_dev(ctx.handle, ctypes.byref(map.info), len(probs), arr, ptr(d_mps), ptr(d_md),
+                                 ptr(d_bad), len(map.mps), ctx.stream))
+    ctx.sync()
+    res = torch.stack(d_res).cpu().numpy().reshape(len(kfs), m, 2)
+    epoch0 = map.desc_epoch[pts].copy()
+    for j, k in enumerate(kfs):
+        kp = res[j, :, 0].copy()
+        # inside one call only the candidate at hand has its descriptor recomputed, after its own search
+        dirty = np.nonzero(_dirty(map, pts, epoch0))[0]
+        if len(dirty):
+            kp[dirty], _ = fuse_sim3(map.info, map.kf_kps[k], map.kf_desc[k], Scw[k], pts[dirty], map.slots[k],
+                                     map.mps, map.mp_desc, map.mp_bad, th, ctx)
+        found = map.get_map_points(k)  # spAlreadyFound, taken once (:1726)
+        for i in range(m):
+            p = int(pts[i])
+            if kp[i] < 0 or map.mp_bad[p] or p in found:  # :1739 on the live map
+                continue
+            idx = int(kp[i])
+            occ = int(map.slots[k][idx])
+            if occ >= 0:
+                if not map.mp_bad[occ]:
+                    map.replace(occ, p)
+                    out["actions"][k].append((p, idx, "replace", occ))
+                else:
+                    out["actions"][k].append((p, idx, "keep", occ))
+            else:
+                map.add_observation(p, k, idx)
+                map.add_map_point(k, p, idx)
+                out["actions"][k].append((p, idx, "add", -1))
+            out["nFused"][k] += 1
+    return out
+
+
+def loop_fusion(map, cur_kf, current_matched_points) -> None:
+    """The loop fusion block of CorrectLoop (LoopClosing.cc:508-525) on a
+    :class:`~gf_orb_slam_amd.loopmap.LoopMap`: slot i of the current keyframe
+    takes the loop point matched to it, the point it held is replaced by it.
+    The reference asks neither point for isBad() here; neither does this."""
+    cur_kf = int(cur_kf)
+    for i, loop_mp in enumerate(np.asarray(current_matched_points, np.int64).reshape(-1)):
+        if loop_mp < 0:
+            continue
+        loop_mp, cur_mp = int(loop_mp), int(map.slots[cur_kf][i])
+        if cur_mp >= 0:
+            map.replace(cur_mp, loop_mp)
+        else:
+            map.add_map_point(cur_kf, loop_mp, i)
+            map.add_observation(loop_mp, cur_kf, i)
+            map.compute_distinctive_descriptors([loop_mp])
+
+
+def loop_connections(map, connected_kfs) -> dict:
+    """The LoopConnections loop of CorrectLoop (LoopClosing.cc:533-552):
+    connected_kfs is mvpCurrentConnectedKFs (the current keyframe's covisibles,
+    then the current keyframe). Each gets UpdateConnections; what is new among
+    its connected keyframes, and not one of connected_kfs, is a loop connection.
+    -> dict keyframe -> sorted list, the argument OptimizeEssentialGraph takes."""
+    connected = [int(k) for k in connected_kfs]
+    out = {}
+    for k in connected:
+        previous = list(map.ordered[k])
+        map.update_connections(k)
+        out[k] = sorted(map.get_connected_keyframes(k) - set(previous) - set(connected))
+    return out
+
+
+def correct_loop(map, cur_kf, matched_kf, gScw, current_matched_points, loop_points, ctx=None) -> dict:
+    """LoopClosing::CorrectLoop (LoopClosing.cc:426-560) on a
+    :class:`~gf_orb_slam_amd.loopmap.LoopMap`, from an accepted loop of
+    :func:`compute_sim3_loop`: cur_kf / matched_kf are mpCurrentKF / mpMatchedKF,
+    gScw is mg2oScw (8 doubles), current_matched_points is
+    mvpCurrentMatchedPoints (per slot of the current keyframe, -1 = NULL) and
+    loop_points is mvpLoopMapPoints.
+
+    UpdateConnections of the current keyframe; the Sim3 propagation
+    (:func:`propagate_loop_correction` and ``gf_correct_loop_points``), keyframe
+    by keyframe in index order: its points' UpdateNormalAndDepth against the
+    poses as they stand, SetPose, UpdateConnections; the loop fusion block;
+    :func:`search_and_fuse`; the LoopConnections loop;
+    ``Optimizer.OptimizeEssentialGraph`` with its write-back and
+    UpdateNormalAndDepth; the mutual loop edge. RequestStop,
+    ForceRelocalisation, SetFlagAfterBA and mLastLoopKFid are the caller's.
+    -> the essential-graph result dict plus ``LoopConnections``, ``fuse`` (the
+    report of search_and_fuse), ``CorrectedSim3`` and ``NonCorrectedSim3``."""
+    from .optimizer import Optimizer
+
+    cur_kf, matched_kf = int(cur_kf), int(matched_kf)
+    map.update_connections(cur_kf)
+    connected = list(map.ordered[cur_kf]) + [cur_kf]  # mvpCurrentConnectedKFs
+    # a point already corrected for this keyframe is passed as bad: the propagation leaves it alone
+    skip = map.mp_bad | (map.corrected_by == cur_kf)
+    pr = propagate_loop_correction(map.Tcw, cur_kf, connected[:-1], gScw, map.slots, map.mps["pos"], skip, ctx)
+    non, cor = pr["NonCorrectedSim3"], pr["CorrectedSim3"]
+    moved = pr["corrected_ref"] >= 0
+    map.mps["pos"][moved] = pr["pos"][moved]
+    map.corrected_by[moved] = cur_kf
+    map.corrected_ref[moved] = pr["corrected_ref"][moved]
+    for k in sorted(cor):
+        map.update_normal_and_depth(np.nonzero(moved & (pr["corrected_ref"] == k))[0])
+        map.set_pose(k, pr["Tcw"][k])
+        map.update_connections(k)
+    loop_fusion(map, cur_kf, current_matched_points)
+    fuse = search_and_fuse(map, cor, loop_points, 4, ctx)
+    LoopConnections = loop_connections(map, connected)
+    out = Optimizer.OptimizeEssentialGraph(map.to_essgraph_map(), matched_kf, cur_kf, gScw, non, cor, LoopConnections,
+                                           ctx)
+    map.Tcw[:] = out["Tcw"]
+    good = ~map.mp_bad
+    map.mps["pos"][good] = out["pos"][good]
+    map.update_normal_and_depth(np.nonzero(good)[0])
+    map.add_loop_edge(matched_kf, cur_kf)
+    map.add_loop_edge(cur_kf, matched_kf)
+    out.update(LoopConnections=LoopConnections, fuse=fuse, CorrectedSim3=cor, NonCorrectedSim3=non)
+    return out

@@ -874,6 +874,43 @@ int gf_search_kf_sim3_projection(gf_ctx* ctx, const gf_frame_info* fi, const flo
                                  const uint8_t* desc, int n, const gf_map_point* mps, const uint8_t* mp_desc,
                                  const uint8_t* mp_bad, int nmp, const int32_t* points, int npoints, int32_t* matched,
                                  int th, int* nmatches);
+/* ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, vpPoints, th)
+ * (src/ORBmatcher.cc:1710-1839) up to the choice of bestIdx (:1816), the
+ * search LoopClosing::SearchAndFuse (src/LoopClosing.cc:572-585) runs for every
+ * keyframe of CorrectedSim3. Host arrays, one keyframe, shaped like
+ * gf_search_kf_sim3_projection: Scw is decomposed as at :1719-1723, points are
+ * map point ids in list order, kf_mp[k] is the id at slot k or -1. A candidate
+ * that isBad() or is a non-bad point of the slot table (spAlreadyFound, :1726,
+ * :1739) is skipped. Result per candidate: kp = the keypoint with
+ * bestDist <= TH_LOW after the exits of :1739-1816, else -1; dist = its
+ * distance, else -1. KeyFrame::GetFeaturesInArea order decides ties. What
+ * :1819-1833 does with kp depends on the live map (the occupant of the slot
+ * may have been replaced by an earlier candidate) and is the caller's. */
+typedef struct gf_fuse_sim3_result {
+    int32_t kp, dist;
+} gf_fuse_sim3_result;
+int gf_fuse_sim3(gf_ctx* ctx, const gf_frame_info* fi, const float Scw[16], const gf_keypoint* kps, const uint8_t* desc,
+                 int n, const int32_t* kf_mp, const gf_map_point* mps, const uint8_t* mp_desc, const uint8_t* mp_bad,
+                 int nmp, const int32_t* points, int npoints, float th, gf_fuse_sim3_result* res);
+/* Device family: the nprob (keyframe, candidate list) searches of one
+ * SearchAndFuse in one launch. The problem array is host memory, copied at the
+ * call; every pointer in it, and d_mps / d_mp_desc / d_mp_bad (nmp rows, shared
+ * by all problems, d_mp_bad optional), is a device pointer. A long candidate
+ * list is spread over several workgroups. Ids outside [0, nmp) give kp = -1. */
+typedef struct gf_fuse_sim3_problem {
+    float Scw[16];
+    const gf_keypoint* kps;
+    const uint8_t* desc;
+    int32_t n;
+    const int32_t* kf_mp;
+    const int32_t* points;
+    int32_t npoints;
+    float th;
+    gf_fuse_sim3_result* res;
+} gf_fuse_sim3_problem;
+int gf_fuse_sim3_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, const gf_fuse_sim3_problem* probs,
+                     const gf_map_point* d_mps, const uint8_t* d_mp_desc, const uint8_t* d_mp_bad, int nmp,
+                     void* stream);
 
 /* ------------------------------------------------ essential graph (loop correction)
  * Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1768-2017), the 7-DoF
