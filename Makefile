@@ -79,6 +79,14 @@ all: $(LOOPFUSEREF)
 $(LOOPFUSEREF): tests/helpers/loopfuse_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of KeyFrameDatabase::add / erase /
+# DetectLoopCandidates and LoopClosing::DetectLoop
+# (tests/test_loopdetect_cpu.py, tests/test_loopdetect_gpu.py), same flags
+LOOPDETECTREF = tests/helpers/libloopdetectref.so
+all: $(LOOPDETECTREF)
+$(LOOPDETECTREF): tests/helpers/loopdetect_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

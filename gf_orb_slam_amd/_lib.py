@@ -149,6 +149,7 @@ _PROTOS = {
     "gf_vocab_create": [_P, _P, _P],
     "gf_vocab_load": [_P, _P, _P],
     "gf_vocab_info": [_P, _P, _P, _P, _P],
+    "gf_vocab_scoring": [_P, _P, _P],
     "gf_vocab_destroy": [_P],
     "gf_bow_transform": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "gf_bow_transform_dev": [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -173,6 +174,17 @@ _PROTOS = {
     "gf_essgraph_plan_destroy": [_P],
     "gf_optimize_essential_graph": [_P, _P, _P],
     "gf_correct_loop_points": [_P, _I, _P, _P, _P, _I, _P, _P, _P],
+    "gf_loopdb_create": [_P, _P],
+    "gf_loopdb_destroy": [_P],
+    "gf_loopdb_size": [_P, _P, _P],
+    "gf_loopdb_clear": [_P],
+    "gf_loopdb_insert": [_P, _P, _P, _I, _P],
+    "gf_loopdb_insert_dev": [_P, _P, _P, _P, _I, _I, _P, _P],
+    "gf_loopdb_add": [_P, _I],
+    "gf_loopdb_erase": [_P, _I],
+    "gf_bow_score": [_I, _P, _P, _I, _P, _P, _I, _P],
+    "gf_loopdb_scores": [_P, _I, _P, _I, _P],
+    "gf_detect_loop_candidates": [_P, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P],
     "gf_local_ba": [_P, _P, _P],
     "gf_ba_plan_create": [_P, _I, _P, _P],
     "gf_ba_plan_solve": [_P, _P, _P],

@@ -113,6 +113,21 @@ class ORBVocabulary:
         return (words[:nw.value].copy(), values[:nw.value].copy(),
                 FeatureVector(nodes[:nfv].copy(), start[:nfv + 1].copy(), feats[:start[nfv]].copy()))
 
+    def scoring(self) -> int:
+        """The vocabulary's ScoringType (0 = L1_NORM), read from the handle."""
+        sc = ctypes.c_int()
+        check(lib().gf_vocab_scoring(self.handle, ctypes.byref(sc), None))
+        return sc.value
+
+    def score(self, v1, v2) -> float:
+        """score(v1, v2) (TemplatedVocabulary.h:1213-1217) of two BowVectors
+        given as (words, values), with this vocabulary's scoring type:
+        L1Scoring::score in double on the host (abi.h gf_bow_score); any other
+        type raises GF_ERR_UNSUPPORTED."""
+        from .loopdetect import bow_score
+
+        return bow_score(v1, v2, self.scoring())
+
     def close(self) -> None:
         if self.handle:
             lib().gf_vocab_destroy(self.handle)

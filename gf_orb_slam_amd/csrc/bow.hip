@@ -714,6 +714,13 @@ int gf_vocab_info(gf_vocab* v, int* k, int* L, int* nnodes, int* nwords) {
     return GF_OK;
 }
 
+int gf_vocab_scoring(gf_vocab* v, int* scoring, int* weighting) {
+    GF_CHECK(v, GF_ERR_ARG, "null vocab");
+    if (scoring) *scoring = v->scoring;
+    if (weighting) *weighting = v->weighting;
+    return GF_OK;
+}
+
 int gf_bow_transform_dev(gf_vocab* v, int nframes, const uint8_t* d_desc, const int32_t* d_n, int cap, int levelsup,
                          int32_t* d_words, double* d_values, int32_t* d_nwords, int32_t* d_fv_nodes,
                          int32_t* d_fv_start, int32_t* d_fv_feats, int32_t* d_nfv, void* stream) {

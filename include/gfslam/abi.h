@@ -447,6 +447,9 @@ int gf_vocab_create(gf_ctx* ctx, const gf_vocab_arrays* tree, gf_vocab** out);
 /* gf_vocab_read + gf_vocab_create (main.cc:92-106 picks the loader by suffix). */
 int gf_vocab_load(gf_ctx* ctx, const char* path, gf_vocab** out);
 int gf_vocab_info(gf_vocab* voc, int* k, int* L, int* nnodes, int* nwords);
+/* The vocabulary's ScoringType and WeightingType (BowVector.h:34-53), as
+ * created, loaded or received. */
+int gf_vocab_scoring(gf_vocab* voc, int* scoring, int* weighting);
 int gf_vocab_destroy(gf_vocab* voc);
 
 /* Frame::ComputeBoW (Frame.cc:380-387) = transform(descriptors, mBowVec,
@@ -1008,6 +1011,64 @@ int gf_optimize_essential_graph(gf_ctx* ctx, const gf_essgraph_problem* prob, gf
  * to: nsim x 8 g2o::Sim3 (NonCorrectedSim3 / CorrectedSim3 rows). */
 int gf_correct_loop_points(gf_ctx* ctx, int npts, const float* pos, const uint8_t* bad, const int32_t* sel, int nsim,
                            const double* from, const double* to, float* pos_out);
+
+/* ------------------------------------------------ loop detection (LoopClosing::DetectLoop)
+ * gf_loopdb: the keyframe database of loop closing (KeyFrameDatabase.cc:32-196)
+ * as BowVectors resident on the device in CSR form (words int32 ascending,
+ * values double). A keyframe is a slot: gf_loopdb_insert stores its BowVector
+ * (0 to 4096 words) without listing it -- keyframe 0 never enters the file
+ * (LoopClosing.cc:98-103) yet is scored for minScore (:132-146) -- and
+ * returns the slot, numbered from 0 in insert order. Storage grows by doubling;
+ * no query uploads the database. Each slot carries an add sequence number, -1
+ * while the keyframe is not in the inverted file:
+ *   gf_loopdb_add    KeyFrameDatabase::add (:39-45): the next sequence number;
+ *                    adding a listed slot is GF_ERR_ARG.
+ *   gf_loopdb_erase  KeyFrameDatabase::erase (:47-66): back to -1; a later add
+ *                    puts the keyframe at the back of its words' lists.
+ *   gf_loopdb_clear  KeyFrameDatabase::clear (:68-72): every slot unlisted, the
+ *                    sequence restarts; the stored vectors and slots remain.
+ * The calls of one database run on its context's stream. gf_loopdb_insert_dev
+ * takes frame `frame` of the arrays gf_bow_transform_dev writes (d_words /
+ * d_values strided by cap, d_nwords per frame) on `stream` without a host
+ * synchronisation; the slot reserves cap entries. It orders the two streams
+ * itself with an event in both directions: its copies wait for the work the
+ * context's stream already holds, and the context's later work waits for
+ * them. Its input stays on the device, so it is not validated as
+ * gf_loopdb_insert's is: the words must ascend, be >= 0 and < INT_MAX, and
+ * d_nwords[frame] is clamped to [0, cap].
+ * gf_bow_score: TemplatedVocabulary::score = L1Scoring::score
+ *   (TemplatedVocabulary.h:1213-1217, ScoringObject.cpp:23-68) of two
+ *   BowVectors, host only, in double: the common words' terms fabs(vi - wi) -
+ *   fabs(vi) - fabs(wi) added in ascending word order, then -score / 2.0.
+ *   scoring = the vocabulary's ScoringType; other than L1_NORM (0):
+ *   GF_ERR_UNSUPPORTED.
+ * gf_loopdb_scores: that score on the device, query_slot's vector against each
+ *   of slots[0..n) (listed or not), cast to float as LoopClosing.cc:142 does.
+ * gf_detect_loop_candidates: KeyFrameDatabase::DetectLoopCandidates(pKF,
+ *   minScore) (:75-196) for the keyframe in query_slot. connected = the slots
+ *   of pKF->GetConnectedKeyFrames(); cov_off ([nslots + 1]) / cov =
+ *   mvpOrderedConnectedKeyFrames per slot as gf_reloc_candidates takes them,
+ *   of which GetBestCovisibilityKeyFrames(10) reads the first ten.
+ *   words_out[nslots] = mnLoopWords (0 for slots that are unlisted, connected
+ *   or share no word), score_out[nslots] = mLoopScore, valid where words_out >
+ *   *min_common (= minCommonWords; 0 when nothing shares a word). cands (room
+ *   for nslots) / ncand = the returned vector, in the reference's order. */
+typedef struct gf_loopdb gf_loopdb;
+int gf_loopdb_create(gf_ctx* ctx, gf_loopdb** out);
+int gf_loopdb_destroy(gf_loopdb* db);
+int gf_loopdb_size(gf_loopdb* db, int* nslots, int* nlisted);
+int gf_loopdb_clear(gf_loopdb* db);
+int gf_loopdb_insert(gf_loopdb* db, const int32_t* words, const double* values, int n, int* slot);
+int gf_loopdb_insert_dev(gf_loopdb* db, const int32_t* d_words, const double* d_values, const int32_t* d_nwords,
+                         int cap, int frame, void* stream, int* slot);
+int gf_loopdb_add(gf_loopdb* db, int slot);
+int gf_loopdb_erase(gf_loopdb* db, int slot);
+int gf_bow_score(int scoring, const int32_t* w1, const double* v1, int n1, const int32_t* w2, const double* v2, int n2,
+                 double* score);
+int gf_loopdb_scores(gf_loopdb* db, int query_slot, const int32_t* slots, int n, float* out);
+int gf_detect_loop_candidates(gf_loopdb* db, int query_slot, const int32_t* connected, int nconn,
+                              const int32_t* cov_off, const int32_t* cov, float min_score, int32_t* words_out,
+                              float* score_out, int* min_common, int32_t* cands, int* ncand);
 
 /* ------------------------------------------------ monocular initialisation
  * ORB_SLAM::Initializer (src/Initializer.cc, include/Initializer.h):
