@@ -87,6 +87,14 @@ all: $(LOOPDETECTREF)
 $(LOOPDETECTREF): tests/helpers/loopdetect_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of LocalMapping::CreateNewMapPoints, ComputeF12,
+# KeyFrame::ComputeSceneMedianDepth and MapPointCulling
+# (tests/test_localmap_cpu.py, tests/test_localmap_gpu.py), same flags
+LOCALMAPREF = tests/helpers/liblocalmapref.so
+all: $(LOCALMAPREF)
+$(LOCALMAPREF): tests/helpers/localmap_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

@@ -146,6 +146,8 @@ _PROTOS = {
     "gf_fuse_dev": [_P, _P, _I, _P, _P],
     "gf_search_for_triangulation": [_P, _I, _P, _P, _P, _P, _I, _P, _P],
     "gf_search_for_triangulation_dev": [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P],
+    "gf_create_new_map_points": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "gf_create_new_map_points_dev": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gf_vocab_create": [_P, _P, _P],
     "gf_vocab_load": [_P, _P, _P],
     "gf_vocab_info": [_P, _P, _P, _P, _P],

@@ -421,13 +421,7 @@ __global__ __launch_bounds__(256) void k_match_bow(const BowPair* __restrict__ p
 // sorts (dist, idx2) and takes the first within round(2 best) passing the
 // epipolar test, i.e. the (dist, idx2)-least passing candidate with
 // d <= min(TH_LOW, 2 best): two wave reductions.
-struct TriPair {
-    gf_bow_side a, b;
-    float F[9];
-    float sigma2[16];
-    int32_t nlevels;
-    int32_t* out;
-};
+using TriPair = gf::TriPairDev;
 
 __device__ __forceinline__ bool epipolar_ok(float a, float b, float c, const gf_keypoint& kp2, const TriPair& P) {
     // CheckDistEpipolarLine (ORBmatcher.cc:705-722)
@@ -780,6 +774,16 @@ int gf::bow_transform_gated(gf_vocab* voc, int nframes, const uint8_t* d_desc, c
     if (nframes <= 0) return GF_OK;
     return bow_transform_impl(voc, nframes, d_desc, d_n, d_gate, cap, levelsup, d_words, d_values, d_nwords,
                               d_fv_nodes, d_fv_start, d_fv_feats, d_nfv, tmp, stream);
+}
+
+int gf::search_tri_pairs(gf_ctx* ctx, int check_ori, int npairs, const gf::TriPairDev* d_pairs, int32_t* d_nmatches,
+                         void* stream) {
+    if (npairs <= 0) return GF_OK;
+    hipStream_t s = (hipStream_t)stream;
+    GF_PROF(ctx, s, "k_search_tri");
+    GF_LAUNCH(k_search_tri, npairs, TRI_THREADS, 0, s, d_pairs, check_ori, d_nmatches);
+    GF_HIP(hipGetLastError());
+    return GF_OK;
 }
 
 int gf::match_bow_pairs(gf_ctx* ctx, int mode, float nnratio, int check_ori, int npairs, const gf::BowPairDev* d_pairs,

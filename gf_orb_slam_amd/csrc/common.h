@@ -50,7 +50,7 @@ struct gf_ctx {
     std::vector<hipEvent_t> event_pool;
     std::vector<hipEvent_t> prof_spent;  // stop events of multi-launch scopes that are not read
     // grow-only device scratch for the host-family wrappers (one slot per use)
-    static const int kSlots = 64;
+    static const int kSlots = 66;
     void* ws[kSlots] = {};
     size_t ws_size[kSlots] = {};
     // captured graphs (gf_frontend_capture) alive on this context: their
@@ -177,6 +177,19 @@ struct BowPairDev {
 };
 int match_bow_pairs(gf_ctx* ctx, int mode, float nnratio, int check_ori, int npairs, const BowPairDev* d_pairs,
                     int32_t* d_nmatches, int bcap, void* stream);
+// One ORBmatcher::SearchForTriangulation pair in device memory
+// (gf_search_for_triangulation_dev copies host-built pairs; the
+// CreateNewMapPoints chain lets a kernel write F of each pair).
+struct TriPairDev {
+    gf_bow_side a, b;
+    float F[9];
+    float sigma2[16];
+    int32_t nlevels;
+    int32_t* out;
+};
+// k_search_tri over d_pairs[0..npairs), one workgroup per pair
+int search_tri_pairs(gf_ctx* ctx, int check_ori, int npairs, const TriPairDev* d_pairs, int32_t* d_nmatches,
+                     void* stream);
 int obs_active_match(gf_ctx* ctx, const gf_frame_info* fi, int nframes, const gf_keypoint* d_kps,
                      const uint8_t* d_desc, const int32_t* d_n, int kp_cap, const gf_mp_view* d_views,
                      const uint8_t* d_mp_desc, const uint8_t* d_updated, const double* d_info, const double* d_H,

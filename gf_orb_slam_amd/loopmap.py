@@ -18,7 +18,7 @@ from .orb import KEYPOINT_DTYPE
 
 class LoopMap:
     def __init__(self, info, kf_kps, kf_desc, kf_mp, mps, mp_desc, mp_bad=None, observations=None, kf_bad=None,
-                 distinctive=None, kf_Tcw=None, ref_kf=None, kf_id=None):
+                 distinctive=None, kf_Tcw=None, ref_kf=None, kf_id=None, first_kf=None, found=None, visible=None):
         """info: the FrameInfo every keyframe shares; kf_kps / kf_desc / kf_mp:
         per keyframe its undistorted keypoints, [n, 32] descriptors and slot
         table (map point id per keypoint, -1 = NULL); mps (MAP_POINT_DTYPE),
@@ -29,7 +29,10 @@ class LoopMap:
         ComputeDistinctiveDescriptors used (default: the device's); kf_Tcw
         [nkf, 4, 4]: the poses (default identity); ref_kf [M]: mpRefKF per point
         (default its first observing keyframe, -1 without one); kf_id: mnId
-        per keyframe, strictly increasing (default the index)."""
+        per keyframe, strictly increasing (default the index); first_kf /
+        found / visible [M]: mnFirstKFid, mnFound, mnVisible per point
+        (defaults: the reference keyframe's mnId, 1 and 1, as the constructor
+        at MapPoint.cc:31-34 sets them)."""
         self.info = info
         self.kf_kps = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k in kf_kps]
         self.kf_desc = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in kf_desc]
@@ -55,6 +58,10 @@ class LoopMap:
         self.kf_id = np.arange(self.nkf, dtype=np.int32) if kf_id is None else np.asarray(kf_id, np.int32).copy()
         self.ref_kf = (np.asarray([min(o) if o else -1 for o in self.obs], np.int32).reshape(-1) if ref_kf is None
                        else np.asarray(ref_kf, np.int32).copy())
+        self.first_kf = (np.where(self.ref_kf >= 0, self.kf_id[np.maximum(self.ref_kf, 0)], -1).astype(np.int64)
+                         if first_kf is None else np.asarray(first_kf, np.int64).copy())
+        self.found = np.ones(n, np.int32) if found is None else np.asarray(found, np.int32).copy()
+        self.visible = np.ones(n, np.int32) if visible is None else np.asarray(visible, np.int32).copy()
         self.corrected_by = np.full(n, -1, np.int32)   # mnCorrectedByKF (a keyframe index)
         self.corrected_ref = np.full(n, -1, np.int32)  # mnCorrectedReference
         # the covisibility graph: mConnectedKeyFrameWeights, the ordered covisibles with their weights,
@@ -74,6 +81,41 @@ class LoopMap:
     def add_observation(self, p: int, kf: int, idx: int) -> None:
         """MapPoint::AddObservation (MapPoint.cc:77-81): overwrites."""
         self.obs[p][int(kf)] = int(idx)
+
+    def new_map_point(self, pos, ref_kf: int) -> int:
+        """``new MapPoint(pos, pRefKF, pMap)`` + ``Map::AddMapPoint``
+        (MapPoint.cc:31-51): a point without observations, normal 0, min / max
+        distance 0, mnFirstKFid = the reference keyframe's mnId, mnFound =
+        mnVisible = 1, an all-zero descriptor. Returns its id."""
+        p = len(self.mps)
+        row = np.zeros(1, MAP_POINT_DTYPE)
+        row["pos"] = np.asarray(pos, np.float32).reshape(3)
+        self.mps = np.concatenate([self.mps, row])
+        self.mp_desc = np.concatenate([self.mp_desc, np.zeros((1, 32), np.uint8)])
+        self.mp_bad = np.append(self.mp_bad, False)
+        self.desc_epoch = np.append(self.desc_epoch, np.int64(0))
+        self.obs.append({})
+        self.ref_kf = np.append(self.ref_kf, np.int32(ref_kf))
+        self.first_kf = np.append(self.first_kf, np.int64(self.kf_id[int(ref_kf)]))
+        self.found = np.append(self.found, np.int32(1))
+        self.visible = np.append(self.visible, np.int32(1))
+        self.corrected_by = np.append(self.corrected_by, np.int32(-1))
+        self.corrected_ref = np.append(self.corrected_ref, np.int32(-1))
+        return p
+
+    def set_bad_point(self, p: int) -> None:
+        """MapPoint::SetBadFlag (MapPoint.cc:117-131): the point turns bad, its
+        observations are cleared and every observing keyframe erases the slot
+        the observation named (EraseMapPointMatch(idx))."""
+        p = int(p)
+        obs, self.obs[p] = self.obs[p], {}
+        self.mp_bad[p] = True
+        for kf in sorted(obs):
+            self.slots[kf][obs[kf]] = -1
+
+    def get_found_ratio(self, p: int) -> np.float32:
+        """MapPoint::GetFoundRatio: ``static_cast<float>(mnFound)/mnVisible``."""
+        return np.float32(self.found[p]) / np.float32(self.visible[p])
 
     def replace(self, a: int, b: int) -> None:
         """``a->Replace(b)`` (MapPoint.cc:136-170): a turns bad, its

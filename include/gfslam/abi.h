@@ -648,6 +648,79 @@ int gf_search_for_triangulation_dev(gf_ctx* ctx, int check_ori, int npairs, cons
                                     const gf_bow_side* b, const float* F12, const float* sigma2_b, int nlevels,
                                     int32_t* const* outs, int32_t* d_nmatches, void* stream);
 
+/* ------------------------------------------------ CreateNewMapPoints
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:243-409) with
+ * ComputeF12 (:490-507) and KeyFrame::ComputeSceneMedianDepth
+ * (src/KeyFrame.cc:659-689): the new keyframe `cur` against its covisible
+ * neighbours, in the given order. Per neighbour: the baseline test
+ * (|Ow2 - Ow1| / median scene depth of the neighbour < 0.01 skips it), F12,
+ * SearchForTriangulation of (cur, neighbour), and per match the linear
+ * triangulation (4x4 CV_32F SVD) with the parallax, depth, reprojection
+ * (5.991 sigma2) and scale-consistency tests. An accepted match becomes a
+ * new map point: its id goes into cur's slot table at idx1 and into the
+ * neighbour's at idx2, so the search against the next neighbour skips that
+ * keypoint (ORBmatcher.cc:1466-1469) — the neighbours are a chain, not
+ * independent pairs.
+ *
+ * A keyframe: Tcw (row-major 4x4), its gf_bow_side (side.mp is ignored) and
+ * its writable slot table mp[side.n] (mvpMapPoints: map point id or -1). The
+ * slot tables of cur and of all neighbours are distinct arrays. Both share
+ * fi (one camera, one scale pyramid). mp_pos[nmp][3]: world positions of the
+ * existing points, for the median depth (every slot id in 0..nmp-1 counts,
+ * bad points included: the reference only tests the pointer).
+ * New points get the ids nmp + 0, 1, 2, ... in creation order: neighbour by
+ * neighbour, inside one neighbour by ascending idx1 (vMatchedIndices order).
+ * At most 4096 keypoints per keyframe and 20 neighbours. */
+enum { GF_NEWPTS_MAX_NEIGH = 20 };
+enum { GF_NP_OK = 0, GF_NP_BASELINE = 1, GF_NP_NODEPTH = 2 }; /* per-neighbour status */
+/* where a match left the per-match body (:307-407); -1 = keypoint not matched */
+enum {
+    GF_NP_EXIT_PARALLAX = 0, /* cosParallaxRays < 0 or > 0.9998 (:322)  */
+    GF_NP_EXIT_W0 = 1,       /* x3D(3) == 0 (:337)                      */
+    GF_NP_EXIT_Z1 = 2,       /* z1 <= 0 (:346)                          */
+    GF_NP_EXIT_Z2 = 3,       /* z2 <= 0 (:350)                          */
+    GF_NP_EXIT_REPROJ1 = 4,  /* (:362)                                  */
+    GF_NP_EXIT_REPROJ2 = 5,  /* (:374)                                  */
+    GF_NP_EXIT_DIST0 = 6,    /* dist1 == 0 or dist2 == 0 (:384)         */
+    GF_NP_EXIT_SCALE = 7,    /* (:389)                                  */
+    GF_NP_EXIT_ACCEPTED = 8
+};
+typedef struct gf_newpoints_kf {
+    float Tcw[16];
+    gf_bow_side side;
+    int32_t* mp;
+} gf_newpoints_kf;
+typedef struct gf_newpoints_neigh {
+    int32_t status;     /* GF_NP_BASELINE: skipped at :280; GF_NP_NODEPTH: the neighbour
+                           has no map point (undefined in the reference), skipped */
+    float F12[9];       /* zeros when skipped */
+    float median_depth; /* 0 when GF_NP_NODEPTH */
+    int32_t nmatches;   /* vMatchedIndices.size() */
+    int32_t naccepted;
+} gf_newpoints_neigh;
+typedef struct gf_newpoint {
+    int32_t neighbour, idx1, idx2;
+    float pos[3];
+} gf_newpoint;
+/* Device family: every pointer inside cur / neigh[i] is a device pointer (the
+ * structs are host memory, copied at the call); d_mp_pos, d_report[nneigh],
+ * d_points[cap], d_exits[nneigh][cur->side.n] and d_total[1] are device
+ * memory. Everything is enqueued on `stream` without a host synchronisation:
+ * one set-up launch, then the matcher and the triangulation launch per
+ * neighbour. d_total = number of points created; records beyond cap are
+ * dropped (the slot tables still receive their ids). Entries of d_points past
+ * min(total, cap) are not written. nneigh = 0 writes d_total = 0 only. */
+int gf_create_new_map_points_dev(gf_ctx* ctx, const gf_frame_info* fi, const gf_newpoints_kf* cur, int nneigh,
+                                 const gf_newpoints_kf* neigh, const float* d_mp_pos, int nmp, int check_ori,
+                                 int cap, gf_newpoints_neigh* d_report, gf_newpoint* d_points, int32_t* d_exits,
+                                 int32_t* d_total, void* stream);
+/* Host family: host arrays everywhere, the slot tables updated in place, one
+ * synchronisation at the end. GF_ERR_CAP when total > cap (total holds the
+ * need; the slot tables are not written back). */
+int gf_create_new_map_points(gf_ctx* ctx, const gf_frame_info* fi, const gf_newpoints_kf* cur, int nneigh,
+                             const gf_newpoints_kf* neigh, const float* mp_pos, int nmp, int check_ori, int cap,
+                             gf_newpoints_neigh* report, gf_newpoint* points, int32_t* exits, int* total);
+
 /* ----------------------------------------- local-map assembly
  * Tracking::UpdateReference (Tracking.cc:3689-3706) =
  * UpdateReferenceKeyFrames (:3768-3852) + UpdateReferencePoints (:3708-3766),
