@@ -95,6 +95,15 @@ all: $(LOCALMAPREF)
 $(LOCALMAPREF): tests/helpers/localmap_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of LocalMapping::SearchInNeighbors, plain
+# ORBmatcher::Fuse, MapPoint::Replace / UpdateNormalAndDepth and
+# KeyFrame::UpdateConnections (tests/test_neighbors_cpu.py,
+# tests/test_neighbors_gpu.py), same flags
+NEIGHBORSREF = tests/helpers/libneighborsref.so
+all: $(NEIGHBORSREF)
+$(NEIGHBORSREF): tests/helpers/neighbors_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

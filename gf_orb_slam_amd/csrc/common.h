@@ -50,7 +50,7 @@ struct gf_ctx {
     std::vector<hipEvent_t> event_pool;
     std::vector<hipEvent_t> prof_spent;  // stop events of multi-launch scopes that are not read
     // grow-only device scratch for the host-family wrappers (one slot per use)
-    static const int kSlots = 66;
+    static const int kSlots = 69;
     void* ws[kSlots] = {};
     size_t ws_size[kSlots] = {};
     // captured graphs (gf_frontend_capture) alive on this context: their
@@ -60,6 +60,9 @@ struct gf_ctx {
     // a stream of its own (gf_frontend_set_track_priority): its kernels take
     // the context's scratch slots, so it must be the only front end here
     int frontends = 0;
+    // candidates per workgroup of gf_fuse_search_dev (gf_fuse_search_set_chunk); 256 measured best
+    // ("SearchInNeighbors")
+    int fuse_search_chunk = 256;
     bool track_stream = false;
 };
 

@@ -66,8 +66,12 @@ FrameConst make_frame_const(const gf_frame_info* fi);
 // cell_start[c] itself to the cell's end, and a shift by one entry (top
 // chunk first, so no entry is overwritten before it is read) turns the ends
 // back into starts: no separate cursor array (12 KB of LDS fewer).
-__device__ __forceinline__ void build_grid(const FrameConst& fc, const gf_keypoint* K, int n, const int32_t* kp2mp,
-                                           int* cell_start, int* items, int* claim, int* scratch, int nthreads) {
+// CLAIM = false (build_grid_only): no claim state is loaded, kp2mp and claim
+// are not touched.
+template <bool CLAIM>
+__device__ __forceinline__ void build_grid_impl(const FrameConst& fc, const gf_keypoint* K, int n,
+                                                const int32_t* kp2mp, int* cell_start, int* items, int* claim,
+                                                int* scratch, int nthreads) {
     const int tid = threadIdx.x;
     for (int c = tid; c < NCELLS + 1; c += nthreads) cell_start[c] = 0;
     __syncthreads();
@@ -78,7 +82,7 @@ __device__ __forceinline__ void build_grid(const FrameConst& fc, const gf_keypoi
         int c = (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
         scratch[i] = c;
         if (c >= 0) atomicAdd(&cell_start[c + 1], 1);
-        claim[i] = kp2mp[i];
+        if constexpr (CLAIM) claim[i] = kp2mp[i];
     }
     __syncthreads();
     if (tid < 64) {  // one wave scans the 3072 counts
@@ -122,6 +126,17 @@ __device__ __forceinline__ void build_grid(const FrameConst& fc, const gf_keypoi
         }
     }
     __syncthreads();
+}
+
+__device__ __forceinline__ void build_grid(const FrameConst& fc, const gf_keypoint* K, int n, const int32_t* kp2mp,
+                                           int* cell_start, int* items, int* claim, int* scratch, int nthreads) {
+    build_grid_impl<true>(fc, K, n, kp2mp, cell_start, items, claim, scratch, nthreads);
+}
+
+// The grid alone: cell_start (NCELLS + 1), items (n) and n ints of scratch.
+__device__ __forceinline__ void build_grid_only(const FrameConst& fc, const gf_keypoint* K, int n, int* cell_start,
+                                                int* items, int* scratch, int nthreads) {
+    build_grid_impl<false>(fc, K, n, nullptr, cell_start, items, nullptr, scratch, nthreads);
 }
 
 // Frame::GetFeaturesInArea window (Frame.cc:305-327); false if empty.

@@ -1,10 +1,16 @@
-"""``LocalMapping::CreateNewMapPoints`` (src/LocalMapping.cc:243-409) and
-``MapPointCulling`` (:213-241) on a :class:`~gf_orb_slam_amd.loopmap.LoopMap`.
+"""``LocalMapping::CreateNewMapPoints`` (src/LocalMapping.cc:243-409),
+``SearchInNeighbors`` (:411-488) and ``MapPointCulling`` (:213-241) on a
+:class:`~gf_orb_slam_amd.loopmap.LoopMap`.
 
 The triangulation chain runs on the device (``gf_create_new_map_points``:
 set-up, then SearchForTriangulation and the triangulation kernel per
 neighbour, the new keyframe's slot table carried from one neighbour to the
 next); the map bookkeeping of :393-406 is done here on the host.
+
+SearchInNeighbors searches on the device (``gf_fuse_search_dev``: every target
+keyframe against the new keyframe's points in one launch, then the new
+keyframe against the union of the targets' points) and takes the add / replace
+decisions of ORBmatcher.cc:1690-1703 here on the live map.
 """
 from __future__ import annotations
 
@@ -17,6 +23,7 @@ from .bow import BowSide
 from .orb import default_context
 
 MAX_NEIGHBOURS = 20
+SECOND_NEIGHBOURS = 5
 STATUS = ("ok", "baseline", "nodepth")
 EXITS = ("parallax", "w0", "z1", "z2", "reproj1", "reproj2", "dist0", "scale", "accepted")
 NEWPOINT_DTYPE = np.dtype([("neighbour", np.int32), ("idx1", np.int32), ("idx2", np.int32), ("pos", np.float32, 3)])
@@ -147,3 +154,230 @@ def map_point_culling(map, recent, cur: int):
         else:
             out.append(p)
     return out
+
+
+class _DeviceMap:
+    """The whole-map arrays of a LoopMap resident on the device for one
+    SearchInNeighbors: positions, normals and distance bounds are uploaded
+    once (nothing in :436-468 writes them), descriptor rows and bad flags again
+    only where they changed since the last search; a keyframe's keypoints and
+    descriptors once."""
+
+    def __init__(self, map, ctx):
+        import torch
+
+        self.map, self.ctx, self.torch = map, ctx, torch
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.d_mps, self.d_md = self._t(map.mps.view(np.uint8)), self._t(map.mp_desc)
+        self.d_bad = self._t(map.mp_bad.astype(np.uint8))
+        self.epoch, self.bad = map.desc_epoch.copy(), map.mp_bad.copy()
+        self.kf_bufs = {}
+
+    def _t(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def _refresh(self):
+        m = self.map
+        rows = np.nonzero(m.desc_epoch != self.epoch)[0]
+        if len(rows):
+            self.d_md[self._t(rows)] = self._t(m.mp_desc[rows])
+            self.epoch[rows] = m.desc_epoch[rows]
+        rows = np.nonzero(m.mp_bad != self.bad)[0]
+        if len(rows):
+            self.d_bad[self._t(rows)] = self._t(m.mp_bad[rows].astype(np.uint8))
+            self.bad[rows] = m.mp_bad[rows]
+
+    def search(self, problems, th):
+        """One ``gf_fuse_search_dev`` launch against the map as it stands.
+        problems: (keyframe, candidate ids, skip bytes) per problem. -> kp per
+        problem."""
+        from .matcher import FuseSearchProblem, camera_center
+
+        m, torch = self.map, self.torch
+        self._refresh()
+        keep, pts_bufs, probs, d_res = [], {}, [], []
+        for k, pts, skip in problems:
+            n = len(m.kf_kps[k])
+            if k not in self.kf_bufs:  # a keyframe listed twice is uploaded once
+                self.kf_bufs[k] = (self._t(m.kf_kps[k].view(np.uint8)), self._t(m.kf_desc[k])) if n else (None, None)
+            if id(pts) not in pts_bufs:  # the forward problems share one candidate list
+                pts_bufs[id(pts)] = self._t(np.asarray(pts, np.int32))
+            d_pts, d_skip = pts_bufs[id(pts)], self._t(np.asarray(skip, np.uint8))
+            r = torch.empty(len(pts) * 2, dtype=torch.int32, device=self.dev)
+            keep.append(d_skip)
+            d_res.append(r)
+            kb = self.kf_bufs[k]
+            probs.append(FuseSearchProblem.make(m.Tcw[k], camera_center(m.Tcw[k]), kb[0], kb[1], n, d_pts, d_skip,
+                                                len(pts), th, r))
+        arr = (FuseSearchProblem * len(probs))(*probs)
+        torch.cuda.current_stream().synchronize()  # the uploads above ran on torch's stream
+        check(lib().gf_fuse_search_dev(self.ctx.handle, ctypes.byref(m.info), len(probs), arr, ptr(self.d_mps),
+                                       ptr(self.d_md), ptr(self.d_bad), len(m.mps), self.ctx.stream))
+        self.ctx.sync()
+        return [r.cpu().numpy().reshape(-1, 2)[:, 0].copy() for r in d_res]
+
+
+def _in_keyframe(map, pts, k):
+    """Per candidate: NULL, isBad() or IsInKeyFrame(k) (ORBmatcher.cc:1611-1615)
+    on the live map."""
+    return np.asarray([p < 0 or bool(map.mp_bad[p]) or map.is_in_keyframe(p, k) for p in (int(q) for q in pts)],
+                      np.uint8)
+
+
+def _fuse_walk(map, dmap, k, pts, kp, epoch, th, stats):
+    """The candidate loop of one ``Fuse(k, pts)`` call on the live map, kp the
+    search results made with the descriptors of ``epoch``. -> (rows, nFused)."""
+    def search(idx, key="researched"):
+        sub = np.ascontiguousarray(pts[idx])
+        new = dmap.search([(k, sub, _in_keyframe(map, sub, k))], th)[0]
+        stats[key] += len(idx)
+        stats["changed"] += int(np.count_nonzero(new != kp[idx]))
+        kp[idx] = new
+        epoch[idx] = map.desc_epoch[pts[idx]]
+
+    kp, epoch = kp.copy(), epoch.copy()
+    valid = np.nonzero(pts >= 0)[0]
+    stale = valid[map.desc_epoch[pts[valid]] != epoch[valid]]
+    stale = stale[_in_keyframe(map, pts[stale], k) == 0]  # the others leave at :1614 whatever their descriptor
+    if len(stale):
+        search(stale)
+    rows, nfused = [], 0
+    for i in valid:
+        p = int(pts[i])
+        if map.mp_bad[p] or map.is_in_keyframe(p, k):  # :1614 on the live map
+            continue
+        if map.desc_epoch[p] != epoch[i]:       # changed inside this call: only where a slot table and an
+            search(np.asarray([i]), "in_call")  # observation map disagree (see search_in_neighbors)
+        if kp[i] < 0:
+            continue
+        idx = int(kp[i])
+        occ = int(map.slots[k][idx])
+        if occ >= 0:
+            if not map.mp_bad[occ]:
+                map.replace(p, occ)  # pMP->Replace(pMPinKF): the candidate goes, the occupant stays
+                rows.append((p, idx, "replace", occ))
+            else:
+                rows.append((p, idx, "keep", occ))
+        else:
+            map.add_observation(p, k, idx)
+            map.add_map_point(k, p, idx)
+            rows.append((p, idx, "add", -1))
+        nfused += 1
+    return rows, nfused
+
+
+def fuse_targets(map, cur: int):
+    """vpTargetKFs of SearchInNeighbors (:414-433), stamping
+    ``map.fuse_target_for`` as it goes. Only first neighbours are stamped, so a
+    second neighbour can be listed more than once."""
+    cur = int(cur)
+    cur_id = int(map.kf_id[cur])
+    targets = []
+    for k in [int(k) for k in map.ordered[cur][:MAX_NEIGHBOURS]]:
+        if map.kf_bad[k] or map.fuse_target_for[k] == cur_id:
+            continue
+        targets.append(k)
+        map.fuse_target_for[k] = cur_id
+        for k2 in [int(q) for q in map.ordered[k][:SECOND_NEIGHBOURS]]:
+            if map.kf_bad[k2] or map.fuse_target_for[k2] == cur_id or int(map.kf_id[k2]) == cur_id:
+                continue
+            targets.append(k2)
+    return targets
+
+
+def search_in_neighbors(map, cur: int, th: float = 3.0, ctx=None) -> dict:
+    """LocalMapping::SearchInNeighbors (:411-488) on a LoopMap for the new
+    keyframe ``cur``, in the reference's order.
+
+    Targets (:414-433): :func:`fuse_targets`.
+
+    Forward (:436-444): the candidate list is ``cur``'s slot table, taken once.
+    One ``gf_fuse_search_dev`` launch searches every target (duplicates
+    included) against the map as it stands, ``skip`` read from the observation
+    map. The targets are then walked in list order and the candidates in list
+    order on the host, where ORBmatcher.cc:1690-1703 runs on the live map.
+
+    Why the launch's results hold at a candidate's turn. A search reads the
+    candidate's position, normal and distance bounds (nothing in :436-468
+    writes them), the keyframe (constant) and the candidate's descriptor.
+    ``MapPoint::Replace`` recomputes the survivor's descriptor and nothing else
+    does, so ``LoopMap.desc_epoch`` names every search that is out of date;
+    before a target's turn those candidates are searched again in one small
+    call on the device-resident map (:class:`_DeviceMap`: only the descriptor
+    rows and flags that changed are uploaded again). A candidate that is bad or in the keyframe at the launch is still so
+    at its turn, which makes both a safe prefilter: a bad point stays bad, and
+    an observation leaves a point's map only when ``Replace`` or ``SetBadFlag``
+    empties the whole map and turns the point bad. Inside one ``Fuse`` call a
+    descriptor changes only through ``pMP->Replace(pMPinKF)``, and the
+    survivor ``pMPinKF`` sits in the keyframe's slot table: when it also is a
+    later candidate of the same call it observes the keyframe and leaves at
+    :1614 without a search, so no candidate's descriptor changes between the
+    start of a call and its own search. That last step leans on the slot
+    table and the observation map agreeing, which the map does not promise
+    (docs/ORACLE_ASSUMPTIONS.md A26); the walk therefore compares the epoch
+    again at the candidate's turn and searches that one candidate again if it
+    moved, so the result is the serial one either way.
+
+    Backward (:446-468): the candidates are the targets' slot tables after the
+    forward walk, in list order, non-NULL, not bad, first occurrence by
+    ``map.fuse_candidate_for``; one ``gf_fuse_search_dev`` problem for ``cur``
+    (spread over candidate chunks), applied on the live map by the same walk. A
+    later candidate that picks a slot an earlier one filled finds it as the
+    occupant and is replaced by it.
+
+    Update (:472-487): ``compute_distinctive_descriptors`` then
+    ``update_normal_and_depth_batch`` once over the non-bad points of ``cur``
+    instead of both per point in turn: each reads only the point's own
+    observations, the keyframes' descriptors and poses and the point's
+    position, and writes only the point's own descriptor, normal and distance
+    bounds, which the other call on another point never reads. Then
+    ``update_connections(cur)``.
+
+    -> report dict: ``targets``; ``forward``: per target ``dict(kf, rows,
+    nFused)`` with rows ``(point, kp, "add" | "replace" | "keep", other)``;
+    ``researched`` / ``research_changed``: candidates searched again and how
+    many of them changed kp, ``researched_in_call`` those of them searched again
+    at their own turn (0 on a map whose tables and observations agree); ``candidates``, ``backward`` (``rows``,
+    ``nFused``); ``updated``: the point ids of the update pass."""
+    cur = int(cur)
+    cur_id = int(map.kf_id[cur])
+    ctx = ctx or default_context()
+    stats = dict(researched=0, in_call=0, changed=0)
+    targets = fuse_targets(map, cur)
+    dmap = None
+    # forward
+    pts = map.slots[cur].astype(np.int32).copy()  # vpMapPointMatches, taken once (:438)
+    forward = []
+    if targets and len(pts):
+        epoch = map.desc_epoch[np.maximum(pts, 0)] if len(map.mps) else np.zeros(len(pts), np.int64)
+        dmap = _DeviceMap(map, ctx)
+        kps = dmap.search([(k, pts, _in_keyframe(map, pts, k)) for k in targets], th)
+        for k, kp in zip(targets, kps):
+            rows, nf = _fuse_walk(map, dmap, k, pts, kp, epoch, th, stats)
+            forward.append(dict(kf=k, rows=rows, nFused=nf))
+    else:
+        forward = [dict(kf=k, rows=[], nFused=0) for k in targets]
+    # backward
+    cand = []
+    for k in targets:
+        for p in map.slots[k]:
+            p = int(p)
+            if p < 0 or map.mp_bad[p] or map.fuse_candidate_for[p] == cur_id:
+                continue
+            map.fuse_candidate_for[p] = cur_id
+            cand.append(p)
+    cand = np.asarray(cand, np.int32)
+    back_rows, back_nf = [], 0
+    if len(cand):
+        epoch = map.desc_epoch[cand].copy()
+        dmap = dmap or _DeviceMap(map, ctx)
+        kp = dmap.search([(cur, cand, _in_keyframe(map, cand, cur))], th)[0]
+        back_rows, back_nf = _fuse_walk(map, dmap, cur, cand, kp, epoch, th, stats)
+    # update
+    ids = list(dict.fromkeys(int(p) for p in map.slots[cur] if p >= 0 and not map.mp_bad[p]))  # each once
+    map.compute_distinctive_descriptors(ids)
+    map.update_normal_and_depth_batch(ids, ctx)
+    map.update_connections(cur)
+    return dict(targets=targets, forward=forward, researched=stats["researched"] + stats["in_call"],
+                researched_in_call=stats["in_call"], research_changed=stats["changed"],
+                candidates=[int(p) for p in cand], backward=dict(rows=back_rows, nFused=back_nf), updated=ids)

@@ -64,6 +64,10 @@ class LoopMap:
         self.visible = np.ones(n, np.int32) if visible is None else np.asarray(visible, np.int32).copy()
         self.corrected_by = np.full(n, -1, np.int32)   # mnCorrectedByKF (a keyframe index)
         self.corrected_ref = np.full(n, -1, np.int32)  # mnCorrectedReference
+        # mnFuseTargetForKF per keyframe / mnFuseCandidateForKF per point: the mnId of the keyframe whose
+        # SearchInNeighbors stamped it last, -1 = never stamped (docs/ORACLE_ASSUMPTIONS.md A28)
+        self.fuse_target_for = np.full(self.nkf, -1, np.int64)
+        self.fuse_candidate_for = np.full(n, -1, np.int64)
         # the covisibility graph: mConnectedKeyFrameWeights, the ordered covisibles with their weights,
         # mpParent / mbFirstConnection and the loop edges
         self.weights = [dict() for _ in range(self.nkf)]
@@ -101,6 +105,7 @@ class LoopMap:
         self.visible = np.append(self.visible, np.int32(1))
         self.corrected_by = np.append(self.corrected_by, np.int32(-1))
         self.corrected_ref = np.append(self.corrected_ref, np.int32(-1))
+        self.fuse_candidate_for = np.append(self.fuse_candidate_for, np.int64(-1))
         return p
 
     def set_bad_point(self, p: int) -> None:
@@ -200,6 +205,39 @@ class LoopMap:
             self.mps["min_dist"][p] = ((f32(1.0) / sf) * dist) / scales[level]
             self.mps["max_dist"][p] = (sf * dist) * scales[nlev - 1 - level]
             self.mps["normal"][p] = normal * f32(1.0 / len(self.obs[p]))
+
+    def update_normal_and_depth_batch(self, ids, ctx=None) -> None:
+        """:meth:`update_normal_and_depth` of the given points in one
+        ``gf_update_normal_and_depth`` call: the observation rows in
+        observation-map order as CSR, the camera centre of every keyframe, and
+        per point the reference keyframe and the octave of
+        ``observations[pRefKF]`` in it (slot 0 when the reference keyframe does
+        not observe the point, as ``map::operator[]`` gives). A point is
+        independent of every other, so the result is that of the per-point
+        method, bit for bit."""
+        from .matcher import camera_center, update_normal_and_depth
+
+        ids = [int(p) for p in ids]
+        if not ids:
+            return
+        offs, rows = [0], []
+        ref_kf, ref_level = np.full(len(ids), -1, np.int32), np.zeros(len(ids), np.int32)
+        for j, p in enumerate(ids):
+            ref = int(self.ref_kf[p])
+            if not (self.mp_bad[p] or not self.obs[p] or ref < 0 or not len(self.kf_kps[ref])):
+                rows.extend(sorted(self.obs[p]))
+                ref_kf[j] = ref
+                ref_level[j] = int(self.kf_kps[ref]["octave"][self.obs[p].get(ref, 0)])
+            offs.append(len(rows))
+        if not rows:
+            return
+        Ow = np.stack([camera_center(T) for T in self.Tcw]) if self.nkf else np.zeros((0, 3), np.float32)
+        nr, mn, mx = update_normal_and_depth(self.info, self.mps["pos"][ids], offs, rows, Ow, ref_kf, ref_level,
+                                             self.mps["normal"][ids], self.mps["min_dist"][ids],
+                                             self.mps["max_dist"][ids], ctx)
+        self.mps["normal"][ids] = nr
+        self.mps["min_dist"][ids] = mn
+        self.mps["max_dist"][ids] = mx
 
     # ------------------------------------------------------------ KeyFrame
     def set_pose(self, kf: int, Tcw) -> None:

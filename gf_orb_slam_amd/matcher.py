@@ -18,6 +18,8 @@ from .orb import KEYPOINT_DTYPE, default_context
 MAP_POINT_DTYPE = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3), ("min_dist", "<f4"), ("max_dist", "<f4")])
 FUSE_RESULT_DTYPE = np.dtype([("kp", "<i4"), ("action", "<i4"), ("target", "<i4")])
 FUSE_NONE, FUSE_ADD, FUSE_REPLACE, FUSE_KEEP = 0, 1, 2, 3
+FUSE_SEARCH_RESULT_DTYPE = np.dtype([("kp", "<i4"), ("dist", "<i4")])
+FUSE_SEARCH_CHUNK_DEFAULT = 256  # candidates per workgroup of gf_fuse_search_dev (csrc/neighbors.hip)
 MP_VIEW_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("view_cos", "<f4"), ("level", "<i4"), ("in_view", "<i4")])
 assert MAP_POINT_DTYPE.itemsize == 32 and MP_VIEW_DTYPE.itemsize == 20
 
@@ -60,6 +62,28 @@ class FuseProblem(ctypes.Structure):
         p = [None if b is None else b.data_ptr() for b in bufs]
         (q.kps, q.desc, q.kf_mp, q.kf_mp_bad, q.mps, q.mp_desc, q.mp_skip, q.mp_ids, q.res, q.nfused) = p
         q.n, q.m, q.th = n, m, th
+        return q
+
+
+class FuseSearchProblem(ctypes.Structure):
+    """gf_fuse_search_problem: one (keyframe, candidate-id list) of
+    gf_fuse_search_dev; device pointers."""
+
+    _fields_ = [("Tcw", ctypes.c_float * 16), ("Ow", ctypes.c_float * 3), ("th", ctypes.c_float),
+                ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p), ("n", ctypes.c_int32),
+                ("points", ctypes.c_void_p), ("skip", ctypes.c_void_p), ("npoints", ctypes.c_int32),
+                ("res", ctypes.c_void_p)]
+
+    @classmethod
+    def make(cls, Tcw, Ow, kps, desc, n, points, skip, npoints, th, res):
+        """kps .. res: device tensors (None allowed where the count is 0, and
+        for skip)."""
+        q = cls()
+        q.Tcw[:] = [float(x) for x in np.asarray(Tcw, np.float32).reshape(16)]
+        q.Ow[:] = [float(x) for x in np.asarray(Ow, np.float32).reshape(3)]
+        dp = lambda b: None if b is None else b.data_ptr()  # noqa: E731
+        q.kps, q.desc, q.points, q.skip, q.res = dp(kps), dp(desc), dp(points), dp(skip), dp(res)
+        q.n, q.npoints, q.th = int(n), int(npoints), float(th)
         return q
 
 
@@ -199,6 +223,60 @@ def camera_center(Tcw: np.ndarray) -> np.ndarray:
         a, b, d = T[0, c] * T[0, 3], T[1, c] * T[1, 3], T[2, c] * T[2, 3]
         out[c] = -((a + b) + d)
     return out
+
+
+def fuse_search(info, kps, desc, Tcw, points, mps, mp_desc, mp_bad=None, skip=None, th=3.0, Ow=None, ctx=None):
+    """The search of ORBmatcher::Fuse(pKF, vpMapPoints, th)
+    (ORBmatcher.cc:1607-1687) over ``gf_fuse_search``. kps / desc: the
+    keyframe's undistorted keypoints and [n, 32] descriptors; Tcw its pose, Ow
+    its camera centre (default :func:`camera_center`); points: the candidates
+    as map point ids in list order, -1 = NULL; mps, mp_desc, mp_bad: the map;
+    skip (optional, per candidate): IsInKeyFrame(pKF). -> (kp, dist) per
+    candidate: the keypoint it would fuse with and its distance, -1 where it
+    leaves the search."""
+    ctx = ctx or default_context()
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    k, d = c(kps, KEYPOINT_DTYPE), c(desc, np.uint8).reshape(-1, 32)
+    T = c(Tcw, np.float32).reshape(16)
+    O = c(camera_center(T) if Ow is None else Ow, np.float32).reshape(3)  # noqa: E741
+    pts = c(points, np.int32).reshape(-1)
+    mp, md = c(mps, MAP_POINT_DTYPE), c(mp_desc, np.uint8).reshape(-1, 32)
+    bad = None if mp_bad is None else c(np.asarray(mp_bad).astype(np.uint8), np.uint8)
+    sk = None if skip is None else c(np.asarray(skip).astype(np.uint8), np.uint8)
+    res = np.zeros(max(len(pts), 1), FUSE_SEARCH_RESULT_DTYPE)
+    check(lib().gf_fuse_search(ctx.handle, ctypes.byref(info), ptr(T), ptr(O), ptr(k) if len(k) else None,
+                               ptr(d) if len(k) else None, len(k), ptr(mp) if len(mp) else None,
+                               ptr(md) if len(mp) else None, ptr(bad), len(mp), ptr(pts) if len(pts) else None,
+                               ptr(sk), len(pts), ctypes.c_float(th), ptr(res)))
+    res = res[:len(pts)]
+    return res["kp"].copy(), res["dist"].copy()
+
+
+def update_normal_and_depth(info, pos, offsets, obs_kf, kf_Ow, ref_kf, ref_level, normal, min_dist, max_dist,
+                            ctx=None):
+    """MapPoint::UpdateNormalAndDepth (MapPoint.cc:285-324) for many points
+    over ``gf_update_normal_and_depth``: obs_kf[offsets[p]:offsets[p + 1]] are
+    the keyframes observing point p in observation-map order, kf_Ow [nkf, 3]
+    the camera centres, ref_kf / ref_level the reference keyframe and the octave
+    of the point's keypoint in it. -> (normal, min_dist, max_dist): copies of
+    the arguments with the rows of points that have observations and a
+    reference keyframe replaced."""
+    ctx = ctx or default_context()
+    c = lambda a, t: np.ascontiguousarray(a, t)  # noqa: E731
+    X = c(pos, np.float32).reshape(-1, 3)
+    npts = len(X)
+    off, ok = c(offsets, np.int32).reshape(-1), c(obs_kf, np.int32).reshape(-1)
+    Ow = c(kf_Ow, np.float32).reshape(-1, 3)
+    rk, rl = c(ref_kf, np.int32).reshape(-1), c(ref_level, np.int32).reshape(-1)
+    nr = c(normal, np.float32).reshape(-1, 3).copy()
+    mn, mx = c(min_dist, np.float32).reshape(-1).copy(), c(max_dist, np.float32).reshape(-1).copy()
+    assert len(off) == npts + 1 and len(rk) == len(rl) == len(nr) == len(mn) == len(mx) == npts
+    assert len(ok) == (off[-1] if npts else 0)
+    if npts:
+        check(lib().gf_update_normal_and_depth(ctx.handle, ctypes.byref(info), npts, ptr(X), ptr(off),
+                                               ptr(ok) if len(ok) else None, ptr(Ow) if len(Ow) else None, len(Ow),
+                                               ptr(rk), ptr(rl), ptr(nr), ptr(mn), ptr(mx)))
+    return nr, mn, mx
 
 
 def compute_distinctive_descriptors(desc: np.ndarray, offsets: np.ndarray, current: np.ndarray | None = None,

@@ -629,6 +629,72 @@ typedef struct gf_fuse_problem {
 } gf_fuse_problem;
 int gf_fuse_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, const gf_fuse_problem* probs, void* stream);
 
+/* The search half of ORBmatcher::Fuse(pKF, vpMapPoints, th)
+ * (src/ORBmatcher.cc:1607-1687) up to the choice of bestIdx, the searches
+ * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:436-468) runs: candidates
+ * are map point ids into the whole-map arrays mps / mp_desc / mp_bad (nmp rows),
+ * no gathered copy. Tcw (row-major 4x4) and Ow (KeyFrame::GetCameraCenter) come
+ * from the caller as for gf_fuse. points[i] = -1 is a NULL slot (:1611);
+ * skip[i] (optional) is the caller's IsInKeyFrame(pKF) read from the
+ * observation map (:1614). Result per candidate in list order: kp = bestIdx and
+ * dist = bestDist when bestDist <= TH_LOW (:1690), else {-1, -1}; a candidate
+ * with id < 0 or >= nmp, with mp_bad set or with skip set gets {-1, -1}.
+ * KeyFrame::GetFeaturesInArea order decides ties. What :1690-1703 does with kp
+ * depends on the live map (MapPoint::Replace moves observations and turns
+ * candidates bad) and is the caller's. Host arrays, one keyframe. */
+typedef struct gf_fuse_search_result {
+    int32_t kp, dist;
+} gf_fuse_search_result;
+int gf_fuse_search(gf_ctx* ctx, const gf_frame_info* fi, const float* Tcw, const float* Ow, const gf_keypoint* kps,
+                   const uint8_t* desc, int n, const gf_map_point* mps, const uint8_t* mp_desc, const uint8_t* mp_bad,
+                   int nmp, const int32_t* points, const uint8_t* skip, int npoints, float th,
+                   gf_fuse_search_result* res);
+/* Device family: nprob (keyframe, candidate-id list) searches in one launch,
+ * enqueued on stream without synchronising. The problem array is host memory,
+ * copied at the call; every pointer in it, and d_mps / d_mp_desc / d_mp_bad
+ * (nmp rows, shared by all problems, d_mp_bad optional), is a device pointer.
+ * A long candidate list is spread over several workgroups, so one keyframe
+ * against the union of its neighbours' points (:468) fills the machine. At most
+ * 4096 keypoints per keyframe; res entries past npoints are never written. */
+typedef struct gf_fuse_search_problem {
+    float Tcw[16];
+    float Ow[3];
+    float th;
+    const gf_keypoint* kps;
+    const uint8_t* desc;
+    int32_t n;
+    const int32_t* points;
+    const uint8_t* skip;
+    int32_t npoints;
+    gf_fuse_search_result* res;
+} gf_fuse_search_problem;
+int gf_fuse_search_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, const gf_fuse_search_problem* probs,
+                       const gf_map_point* d_mps, const uint8_t* d_mp_desc, const uint8_t* d_mp_bad, int nmp,
+                       void* stream);
+/* Candidates per workgroup of gf_fuse_search_dev on this context, for
+ * measurements (scripts/neighbors_bench.py); the default, 256, is the measured
+ * choice. A value outside [64, 65536] is an error and changes nothing. The
+ * results do not depend on it. */
+int gf_fuse_search_set_chunk(gf_ctx* ctx, int chunk);
+
+/* MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:285-324) for npts points.
+ * pos[npts][3]; the observing keyframes of point p are obs_kf[offsets[p] ..
+ * offsets[p + 1]) in observation-map order (the order of the float sum at
+ * :302-309); kf_Ow[nkf][3] the camera centres; ref_kf[p] = mpRefKF and
+ * ref_level[p] = the octave of observations[pRefKF] in it (:313), computed by
+ * the caller; the pyramid comes from fi. cv::norm is a double sum cast to
+ * float and Mat / scalar one float factor (float)(1 / scalar). normal, min_dist
+ * and max_dist are in / out: a point with an empty row or ref_kf < 0, where
+ * the reference divides by zero, is left untouched. Host arrays. */
+int gf_update_normal_and_depth(gf_ctx* ctx, const gf_frame_info* fi, int npts, const float* pos, const int32_t* offsets,
+                               const int32_t* obs_kf, const float* kf_Ow, int nkf, const int32_t* ref_kf,
+                               const int32_t* ref_level, float* normal, float* min_dist, float* max_dist);
+/* Device family: device pointers, enqueued on stream without synchronising. */
+int gf_update_normal_and_depth_dev(gf_ctx* ctx, const gf_frame_info* fi, int npts, const float* d_pos,
+                                   const int32_t* d_offsets, const int32_t* d_obs_kf, const float* d_kf_Ow, int nkf,
+                                   const int32_t* d_ref_kf, const int32_t* d_ref_level, float* d_normal,
+                                   float* d_min_dist, float* d_max_dist, void* stream);
+
 /* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, ...) (src/ORBmatcher.cc:
  * 1426-1588): keypoints of a (pKF1) and b (pKF2) without a map point
  * (mp < 0) that share a FeatureVector node; best distance <= TH_LOW, the
