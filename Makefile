@@ -104,6 +104,15 @@ all: $(NEIGHBORSREF)
 $(NEIGHBORSREF): tests/helpers/neighbors_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of LocalMapping::KeyFrameCulling,
+# KeyFrame::SetBadFlag / EraseConnection / SetErase and
+# MapPoint::EraseObservation / SetBadFlag (tests/test_kfcull_cpu.py,
+# tests/test_kfcull_gpu.py), same flags
+KFCULLREF = tests/helpers/libkfcullref.so
+all: $(KFCULLREF)
+$(KFCULLREF): tests/helpers/kfcull_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

@@ -1,5 +1,6 @@
 """``LocalMapping::CreateNewMapPoints`` (src/LocalMapping.cc:243-409),
-``SearchInNeighbors`` (:411-488) and ``MapPointCulling`` (:213-241) on a
+``SearchInNeighbors`` (:411-488), ``MapPointCulling`` (:213-241) and
+``KeyFrameCulling`` (:562-616) on a
 :class:`~gf_orb_slam_amd.loopmap.LoopMap`.
 
 The triangulation chain runs on the device (``gf_create_new_map_points``:
@@ -11,6 +12,10 @@ SearchInNeighbors searches on the device (``gf_fuse_search_dev``: every target
 keyframe against the new keyframe's points in one launch, then the new
 keyframe against the union of the targets' points) and takes the add / replace
 decisions of ORBmatcher.cc:1690-1703 here on the live map.
+
+KeyFrameCulling counts on the device (``gf_keyframe_culling_counts_dev``: every
+candidate in one launch over flat tables of the map) and runs the decision and
+``KeyFrame::SetBadFlag`` (``LoopMap.set_bad_keyframe``) here on the host.
 """
 from __future__ import annotations
 
@@ -154,6 +159,182 @@ def map_point_culling(map, recent, cur: int):
         else:
             out.append(p)
     return out
+
+
+MAX_KEYPOINTS = 4096
+
+
+def culling_tables(map):
+    """The flat tables ``gf_keyframe_culling_counts`` reads, of a LoopMap as
+    it stands -> (kf_off, octave, slots, mp_bad, obs_off, obs_gkp, where):
+    the observation rows point-major in observation-map order, an entry the
+    global keypoint index ``kf_off[kf] + idx``; ``where[(p, kf)]`` = the
+    entry's position."""
+    n = [len(k) for k in map.kf_kps]
+    if n and max(n) > MAX_KEYPOINTS:
+        raise GFError(-3, "at most 4096 keypoints per keyframe")
+    kf_off = np.zeros(map.nkf + 1, np.int32)
+    kf_off[1:] = np.cumsum(n)
+    octave = np.concatenate([np.zeros(0, np.uint8)] + [k["octave"].astype(np.uint8) for k in map.kf_kps])
+    slots = np.concatenate([np.zeros(0, np.int32)] + list(map.slots)).astype(np.int32)
+    rows = map.observation_rows()
+    obs_off = np.zeros(len(map.mps) + 1, np.int32)
+    obs_off[1:] = np.cumsum(np.bincount(rows[:, 0], minlength=len(map.mps)))
+    obs_gkp = (kf_off[rows[:, 1]] + rows[:, 2]).astype(np.int32)
+    where = {(int(p), int(k)): j for j, (p, k) in enumerate(rows[:, :2])}
+    return kf_off, octave, slots, map.mp_bad.astype(np.uint8), obs_off, obs_gkp, where
+
+
+def keyframe_culling_counts(kf_off, octave, slots, mp_bad, obs_off, obs_gkp, cand, flags=None, ctx=None):
+    """``gf_keyframe_culling_counts`` on host arrays (the counting of
+    LocalMapping.cc:576-611 for every candidate in one launch) -> counts
+    [ncand, 2] = (nmps, nredundant). flags (uint8, one per slot of the whole
+    table, optional) is written in place inside the candidates' ranges."""
+    ctx = ctx or default_context()
+    c = np.ascontiguousarray
+    kf_off, slots, obs_off, obs_gkp, cand = (c(a, np.int32).reshape(-1) for a in (kf_off, slots, obs_off, obs_gkp, cand))
+    octave, mp_bad = c(octave, np.uint8).reshape(-1), c(mp_bad, np.uint8).reshape(-1)
+    if len(octave) != len(slots) or len(obs_off) != len(mp_bad) + 1:
+        raise GFError(-1, "table lengths disagree")
+    if flags is not None and (flags.dtype != np.uint8 or not flags.flags.c_contiguous or len(flags) != len(slots)):
+        raise GFError(-1, "flags: one contiguous uint8 per slot")
+    counts = np.zeros((max(len(cand), 1), 2), np.int32)
+    check(lib().gf_keyframe_culling_counts(ctx.handle, len(kf_off) - 1, ptr(kf_off), ptr(octave), ptr(slots),
+                                           len(mp_bad), ptr(mp_bad), ptr(obs_off), ptr(obs_gkp), len(cand), ptr(cand),
+                                           ptr(counts), ptr(flags)))
+    return counts[:len(cand)]
+
+
+class _CullTables:
+    """The five tables of :func:`culling_tables` for one KeyFrameCulling,
+    resident on the device (uploaded once) unless a host ``counter`` is
+    injected. After a cull only what the surgery touched is written again:
+    -1 over the erased observations (the CSR is never rebuilt), the bad flags
+    of the points that turned bad and -1 in the slots their SetBadFlag
+    cleared."""
+
+    def __init__(self, map, ctx, counter=None):
+        self.map, self.ctx, self.counter = map, ctx, counter
+        (self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off, self.obs_gkp,
+         self.where) = culling_tables(map)
+        self.launches = 0
+        if counter is None:
+            import torch
+
+            self.torch = torch
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+            self.d = [self._t(a) for a in (self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off,
+                                           self.obs_gkp)]
+            torch.cuda.current_stream().synchronize()
+
+    def _t(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def count(self, cand):
+        """One launch over the candidates -> counts [ncand, 2]."""
+        cand = np.ascontiguousarray(cand, np.int32)
+        self.launches += 1
+        if self.counter is not None:
+            return np.asarray(self.counter(self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off,
+                                           self.obs_gkp, cand), np.int32).reshape(-1, 2)
+        torch = self.torch
+        d_cand = self._t(cand)
+        d_counts = torch.empty(len(cand) * 2, dtype=torch.int32, device=self.dev)
+        torch.cuda.current_stream().synchronize()  # the uploads and refreshes ran on torch's stream
+        d = self.d
+        check(lib().gf_keyframe_culling_counts_dev(self.ctx.handle, len(self.kf_off) - 1, len(self.slots), ptr(d[0]),
+                                                   ptr(d[1]), ptr(d[2]), len(self.mp_bad), ptr(d[3]), ptr(d[4]),
+                                                   ptr(d[5]), len(self.obs_gkp), len(cand), ptr(d_cand),
+                                                   ptr(d_counts), None, self.ctx.stream))
+        self.ctx.sync()
+        return d_counts.cpu().numpy().reshape(-1, 2)
+
+    def refresh(self, log):
+        """Point updates after ``set_bad_keyframe`` returned ``log``."""
+        gone = np.asarray([self.where[(p, k)] for p, k, _ in log["observations"]], np.int64)
+        bad = np.asarray(log["points_bad"], np.int64)
+        cleared = np.asarray([self.kf_off[k] + i for k, i in log["cleared"]], np.int64)
+        self.obs_gkp[gone], self.mp_bad[bad], self.slots[cleared] = -1, 1, -1
+        if self.counter is None:
+            for j, rows, v in ((5, gone, -1), (3, bad, 1), (2, cleared, -1)):
+                if len(rows):
+                    self.d[j][self._t(rows)] = v
+
+
+def keyframe_culling(map, cur: int, db=None, ctx=None, counter=None) -> dict:
+    """LocalMapping::KeyFrameCulling (:562-616) on a LoopMap for the current
+    keyframe ``cur``.
+
+    The candidates are a copy of ``map.ordered[cur]`` taken once (:567), walked
+    in that order, the first keyframe (mnId 0) skipped. One
+    ``gf_keyframe_culling_counts_dev`` launch on device-resident tables
+    (:class:`_CullTables`) counts nMPs and nRedundantObservations of every
+    candidate; where nothing is culled that is all the device work. The
+    decision ``nredundant > 0.9 * nmps`` is taken here in double.
+
+    When a candidate K is culled, ``map.set_bad_keyframe(K, db)`` runs on the
+    host, the device copy receives point updates only, and the candidates after
+    K are counted again in one launch before the walk goes on: K's
+    observations are gone from the rows of its points (fewer observations,
+    fewer octave-qualified observers), and the points that fell to two
+    observations turned bad and left other keyframes' nMPs. A candidate before
+    K was already decided on the map of its own turn. A candidate that
+    ``set_bad_keyframe`` deferred (``not_erase``) changed nothing but its
+    ``to_be_erased``, so nothing is refreshed or counted again.
+
+    counter: a callable with the signature of
+    :func:`keyframe_culling_counts` used instead of the device, on host copies
+    of the tables (the CPU tests inject the restatement's).
+
+    -> report dict: ``candidates``; ``per_candidate``: a dict per candidate
+    with ``kf``, ``nmps`` / ``nredundant`` (the counts of its own turn),
+    ``culled``, ``deferred`` and ``recounted`` (how many times it was counted
+    again); ``culled``: the culled keyframes in order; ``points_bad``;
+    ``reparented``: (child, new parent) pairs; ``launches``; ``times``: seconds
+    spent in uploads, launches, the host walk and the refreshes."""
+    import time
+
+    cur = int(cur)
+    cand = [int(k) for k in map.ordered[cur] if map.kf_id[int(k)] != 0]
+    n = len(cand)
+    per = [dict(kf=k, nmps=0, nredundant=0, culled=False, deferred=False, recounted=0) for k in cand]
+    rep = dict(candidates=cand, per_candidate=per, culled=[], points_bad=[], reparented=[], launches=0,
+               times=dict(upload=0.0, launch=0.0, walk=0.0, refresh=0.0))
+    if not n:
+        return rep
+    t = [time.perf_counter()]
+
+    def lap(name):
+        t.append(time.perf_counter())
+        rep["times"][name] += t[-1] - t[-2]
+
+    tables = _CullTables(map, None if counter is not None else (ctx or default_context()), counter)
+    lap("upload")
+    counts = tables.count(cand)
+    lap("launch")
+    for j, k in enumerate(cand):
+        nmps, nred = int(counts[j, 0]), int(counts[j, 1])
+        per[j]["nmps"], per[j]["nredundant"] = nmps, nred
+        if not float(nred) > 0.9 * float(nmps):
+            continue
+        log = map.set_bad_keyframe(k, db)
+        per[j]["deferred"], per[j]["culled"] = log["deferred"], log["erased"]
+        if not log["erased"]:
+            continue
+        rep["culled"].append(k)
+        rep["points_bad"] += log["points_bad"]
+        rep["reparented"] += log["reparented"]
+        lap("walk")
+        tables.refresh(log)
+        lap("refresh")
+        if j + 1 < n:
+            counts[j + 1:] = tables.count(cand[j + 1:])
+            for q in per[j + 1:]:
+                q["recounted"] += 1
+        lap("launch")
+    lap("walk")
+    rep["launches"] = tables.launches
+    return rep
 
 
 class _DeviceMap:

@@ -76,6 +76,9 @@ class LoopMap:
         self.parent = [-1] * self.nkf
         self.first_connection = [True] * self.nkf
         self.loop_edges = [[] for _ in range(self.nkf)]
+        # mbNotErase / mbToBeErased (KeyFrame.cc:474-508)
+        self.not_erase = np.zeros(self.nkf, bool)
+        self.to_be_erased = np.zeros(self.nkf, bool)
 
     # ------------------------------------------------------------ MapPoint
     def is_in_keyframe(self, p: int, kf: int) -> bool:
@@ -117,6 +120,24 @@ class LoopMap:
         self.mp_bad[p] = True
         for kf in sorted(obs):
             self.slots[kf][obs[kf]] = -1
+
+    def erase_observation(self, p: int, kf: int) -> bool:
+        """MapPoint::EraseObservation (MapPoint.cc:83-103): nothing when ``kf``
+        does not observe the point; otherwise the entry goes, a reference
+        keyframe equal to ``kf`` becomes the lowest remaining keyframe (``begin()``
+        of the observation map; with no observation left ``ref_kf`` stays as it
+        is, docs/ORACLE_ASSUMPTIONS.md A30), and a point left with two
+        observations or fewer turns bad. -> whether it turned bad."""
+        p, kf = int(p), int(kf)
+        if kf not in self.obs[p]:
+            return False
+        del self.obs[p][kf]
+        if self.ref_kf[p] == kf and self.obs[p]:
+            self.ref_kf[p] = min(self.obs[p])
+        if len(self.obs[p]) <= 2:
+            self.set_bad_point(p)
+            return True
+        return False
 
     def get_found_ratio(self, p: int) -> np.float32:
         """MapPoint::GetFoundRatio: ``static_cast<float>(mnFound)/mnVisible``."""
@@ -245,9 +266,116 @@ class LoopMap:
         self.Tcw[kf] = np.asarray(Tcw, np.float32).reshape(4, 4)
 
     def add_loop_edge(self, kf: int, other: int) -> None:
-        """KeyFrame::AddLoopEdge: a set."""
+        """KeyFrame::AddLoopEdge (KeyFrame.cc:461-466): a set; the keyframe is
+        not to be erased from now on."""
+        self.not_erase[kf] = True
         if other not in self.loop_edges[kf]:
             self.loop_edges[kf].append(int(other))
+
+    def set_not_erase(self, kf: int) -> None:
+        """KeyFrame::SetNotErase (KeyFrame.cc:474-478)."""
+        self.not_erase[int(kf)] = True
+
+    def set_erase(self, kf: int, db=None):
+        """KeyFrame::SetErase (KeyFrame.cc:480-494): the protection ends unless
+        the keyframe has loop edges, and a SetBadFlag that was deferred
+        meanwhile runs now. -> the log of :meth:`set_bad_keyframe`, or None
+        when none was pending."""
+        kf = int(kf)
+        if not self.loop_edges[kf]:
+            self.not_erase[kf] = False
+        if self.to_be_erased[kf]:
+            return self.set_bad_keyframe(kf, db)
+        return None
+
+    def erase_map_point_match(self, kf: int, idx: int) -> None:
+        """KeyFrame::EraseMapPointMatch(idx)."""
+        self.slots[int(kf)][int(idx)] = -1
+
+    def erase_connection(self, kf: int, other: int) -> None:
+        """KeyFrame::EraseConnection (KeyFrame.cc:596-610)."""
+        if other in self.weights[kf]:
+            del self.weights[kf][other]
+            self.update_best_covisibles(kf)
+
+    def children(self, kf: int) -> set:
+        """KeyFrame::GetChilds of a keyframe that is not bad, derived from the
+        parents: ``{c : parent[c] == kf and not kf_bad[c]}``. mspChildrens
+        needs no state of its own here: a child enters it through
+        ChangeParent / the first UpdateConnections, which also set
+        ``parent[c]``; ChangeParent is called only from SetBadFlag, which moves
+        every child of the keyframe that turns bad to another parent; and
+        EraseChild is called only by a keyframe that turns bad, on its parent.
+        So the set of a keyframe that is not bad is those whose parent it is,
+        less the ones that turned bad."""
+        kf = int(kf)
+        return {c for c in range(self.nkf) if self.parent[c] == kf and not self.kf_bad[c]}
+
+    def set_bad_keyframe(self, kf: int, db=None) -> dict:
+        """KeyFrame::SetBadFlag (KeyFrame.cc:497-588). The first keyframe
+        (mnId 0) returns; a ``not_erase`` keyframe only sets ``to_be_erased``.
+        Otherwise, in the reference's order: EraseConnection(kf) on every key
+        of the weight map (those only: a keyframe that lists ``kf`` without
+        being listed back keeps its entry); EraseObservation(kf) on every
+        non-NULL slot in slot order; the weights and the ordered lists are
+        cleared; the spanning tree is mended (:524-579: the children in index
+        order, each child's ordered covisibles in list order, the parent
+        candidates in index order and compared by mnId, ``w > max`` strict so
+        the first maximum wins; the children without a link go to the original
+        parent); the keyframe turns bad; ``db.erase(kf)`` when a keyframe
+        database is given (its slot is the keyframe index).
+
+        -> log dict: ``erased`` (False: returned or deferred), ``deferred``,
+        ``observations``: the (point, keyframe, slot) entries EraseObservation
+        removed, ``points_bad``: the points that turned bad, ``cleared``: the
+        (keyframe, slot) entries their SetBadFlag erased, ``reparented``:
+        (child, new parent) pairs, all in order."""
+        kf = int(kf)
+        log = dict(erased=False, deferred=False, observations=[], points_bad=[], cleared=[], reparented=[])
+        if self.kf_id[kf] == 0:
+            return log
+        if self.not_erase[kf]:
+            self.to_be_erased[kf] = True
+            log["deferred"] = True
+            return log
+        for other in sorted(self.weights[kf]):
+            self.erase_connection(other, kf)
+        for p in self.slots[kf]:
+            p = int(p)
+            if p < 0 or kf not in self.obs[p]:
+                continue
+            log["observations"].append((p, kf, self.obs[p][kf]))
+            rest = [(k, i) for k, i in sorted(self.obs[p].items()) if k != kf]
+            if self.erase_observation(p, kf):
+                log["points_bad"].append(p)
+                log["cleared"].extend(rest)
+        self.weights[kf], self.ordered[kf], self.ordered_w[kf] = {}, [], []
+        parent = self.parent[kf]
+        candidates = {parent} if parent >= 0 else set()
+        children = sorted(self.children(kf))
+        while children:
+            best, pc, pp = -1, None, None
+            for c in children:
+                for v in self.ordered[c]:
+                    for s in sorted(candidates):
+                        if self.kf_id[v] == self.kf_id[s]:
+                            w = self.weights[c].get(v, 0)  # GetWeight
+                            if w > best:
+                                best, pc, pp = w, c, int(v)
+            if pc is None:
+                break
+            self.parent[pc] = pp  # ChangeParent
+            log["reparented"].append((pc, pp))
+            candidates.add(pc)
+            children.remove(pc)
+        for c in children:
+            self.parent[c] = parent
+            log["reparented"].append((c, parent))
+        self.kf_bad[kf] = True
+        if db is not None:
+            db.erase(kf)
+        log["erased"] = True
+        return log
 
     def to_essgraph_map(self) -> dict:
         """The map dict ``optimizer.EssGraphArrays`` takes."""

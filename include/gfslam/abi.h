@@ -695,6 +695,36 @@ int gf_update_normal_and_depth_dev(gf_ctx* ctx, const gf_frame_info* fi, int npt
                                    const int32_t* d_ref_kf, const int32_t* d_ref_level, float* d_normal,
                                    float* d_min_dist, float* d_max_dist, void* stream);
 
+/* The counting of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:562-616)
+ * for ncand candidate keyframes cand[c] in one launch. The tables are flat:
+ * kf_off[nkf + 1] prefix sums of the keyframes' keypoint counts (nkp =
+ * kf_off[nkf]); octave[nkp] = GetKeyPointUn(i).octave and slots[nkp] =
+ * mvpMapPoints of every keyframe, keyframe-major; mp_bad[nmp]; the observation
+ * maps as CSR rows obs_gkp[obs_off[p] .. obs_off[p + 1]) of global keypoint
+ * indices kf_off[kf'] + idx', point-major in observation-map order, -1 = an
+ * erased observation, which is skipped. For every slot i of candidate K whose
+ * point p has 0 <= p < nmp and !mp_bad[p]: nmps++ (:585); when the row has
+ * more than 3 live entries (:586), those outside [kf_off[K], kf_off[K + 1])
+ * (:594) with octave[g] <= octave[kf_off[K] + i] + 1 (:597) are counted, and
+ * the slot is redundant when they reach 3 (:604). A point in two slots counts
+ * per slot, a point that does not list K counts every observer, and no observer
+ * is tested for isBad(), as in the reference. counts[c] = {nmps, nredundant};
+ * flags (optional, nkp bytes) gets 0 = NULL or bad, 1 = counted, 2 = redundant
+ * inside the candidates' slot ranges and is not written elsewhere. The
+ * decision nredundant > 0.9 * nmps (:613) is a double comparison and the
+ * caller's. Host arrays, synchronous; at most 4096 keypoints per keyframe. */
+int gf_keyframe_culling_counts(gf_ctx* ctx, int nkf, const int32_t* kf_off, const uint8_t* octave, const int32_t* slots,
+                               int nmp, const uint8_t* mp_bad, const int32_t* obs_off, const int32_t* obs_gkp,
+                               int ncand, const int32_t* cand, int32_t* counts, uint8_t* flags);
+/* Device family (src/LocalMapping.cc:562-616): device pointers, the totals nkp
+ * and nobs given by the caller, enqueued on stream without synchronising. An
+ * entry of d_obs_gkp outside [0, nkp) is skipped like -1, a candidate outside
+ * [0, nkf) gets {0, 0}. */
+int gf_keyframe_culling_counts_dev(gf_ctx* ctx, int nkf, int nkp, const int32_t* d_kf_off, const uint8_t* d_octave,
+                                   const int32_t* d_slots, int nmp, const uint8_t* d_mp_bad, const int32_t* d_obs_off,
+                                   const int32_t* d_obs_gkp, int nobs, int ncand, const int32_t* d_cand,
+                                   int32_t* d_counts, uint8_t* d_flags, void* stream);
+
 /* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, ...) (src/ORBmatcher.cc:
  * 1426-1588): keypoints of a (pKF1) and b (pKF2) without a map point
  * (mp < 0) that share a FeatureVector node; best distance <= TH_LOW, the
