@@ -113,6 +113,14 @@ all: $(KFCULLREF)
 $(KFCULLREF): tests/helpers/kfcull_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of Optimizer::LocalBundleAdjustment on a map: the
+# gather, the graph and the write-back, without the solver
+# (tests/test_lbamap_cpu.py, tests/test_lbamap_gpu.py), same flags
+LBAMAPREF = tests/helpers/liblbamapref.so
+all: $(LBAMAPREF)
+$(LBAMAPREF): tests/helpers/lbamap_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

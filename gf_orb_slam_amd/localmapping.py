@@ -16,6 +16,11 @@ decisions of ORBmatcher.cc:1690-1703 here on the live map.
 KeyFrameCulling counts on the device (``gf_keyframe_culling_counts_dev``: every
 candidate in one launch over flat tables of the map) and runs the decision and
 ``KeyFrame::SetBadFlag`` (``LoopMap.set_bad_keyframe``) here on the host.
+
+LocalBundleAdjustment (src/Optimizer.cc:1515-1764) assembles its graph on the
+device (``gf_lba_graph_dev``: the gather, the vertices and the edges from flat
+tables of the map), solves it with ``gf_local_ba_stop`` and applies the outlier
+erasure and the write-back of :1681-1763 here on the host.
 """
 from __future__ import annotations
 
@@ -562,3 +567,258 @@ def search_in_neighbors(map, cur: int, th: float = 3.0, ctx=None) -> dict:
     return dict(targets=targets, forward=forward, researched=stats["researched"] + stats["in_call"],
                 researched_in_call=stats["in_call"], research_changed=stats["changed"],
                 candidates=[int(p) for p in cand], backward=dict(rows=back_rows, nFused=back_nf), updated=ids)
+
+
+# ------------------------------------------------ LocalBundleAdjustment on the map
+class LBATables(ctypes.Structure):
+    """gf_lba_tables: the flat map tables ``gf_lba_graph`` reads."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("nkf", "nkp", "nmp", "nobs", "nlevels", "kf0")] + [
+        (n, ctypes.c_void_p) for n in ("kf_off", "octave", "slots", "kf_bad", "kp_xy", "kf_Tcw", "mp_bad", "mp_pos",
+                                       "obs_off", "obs_gkp", "inv_sigma2")] + [("cam", ctypes.c_float * 4)]
+
+
+class LBAGraphOut(ctypes.Structure):
+    """gf_lba_graph_out: the assembled gf_ba_problem and the write-back's maps."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("counts", "prob_kf", "kf_kind", "kf_Tcw", "kf_cam", "prob_pt", "pt_pos",
+                                               "edge_pt", "edge_kf", "edge_z", "edge_inv_sigma2", "edge_gkp")]
+
+
+# table name, dtype, elements per row, which size it follows (+1: one more row)
+_LBA_TABLES = (("kf_off", np.int32, 1, "nkf+"), ("octave", np.uint8, 1, "nkp"), ("slots", np.int32, 1, "nkp"),
+               ("kf_bad", np.uint8, 1, "nkf"), ("kp_xy", np.float32, 2, "nkp"), ("kf_Tcw", np.float32, 16, "nkf"),
+               ("mp_bad", np.uint8, 1, "nmp"), ("mp_pos", np.float32, 3, "nmp"), ("obs_off", np.int32, 1, "nmp+"),
+               ("obs_gkp", np.int32, 1, "nobs"), ("inv_sigma2", np.float32, 1, "nlevels"))
+# output name, dtype, elements per row, the count it follows (0 keyframes, 1 points, 2 edges)
+_LBA_OUT = (("prob_kf", np.int32, 1, 0), ("kf_kind", np.uint8, 1, 0), ("kf_Tcw", np.float32, 16, 0),
+            ("kf_cam", np.float32, 4, 0), ("prob_pt", np.int32, 1, 1), ("pt_pos", np.float32, 3, 1),
+            ("edge_pt", np.int32, 1, 2), ("edge_kf", np.int32, 1, 2), ("edge_z", np.float32, 2, 2),
+            ("edge_inv_sigma2", np.float32, 1, 2), ("edge_gkp", np.int32, 1, 2))
+MAX_LOCAL_BA_KEYFRAMES = 32
+
+
+def lba_tables(map) -> dict:
+    """The flat tables ``gf_lba_graph`` reads, of a LoopMap as it stands: the
+    five of :func:`culling_tables` (with ``where``), the keyframes' bad flags,
+    undistorted keypoint positions and poses, the points' positions,
+    ``inv_sigma2`` per level, the camera and ``kf0``, the index of the keyframe
+    with mnId 0 (-1 without one)."""
+    from .optimizer import inv_level_sigma2
+
+    kf_off, octave, slots, mp_bad, obs_off, obs_gkp, where = culling_tables(map)
+    xy = [np.zeros((0, 2), np.float32)] + [np.stack([k["x"], k["y"]], axis=1).astype(np.float32) for k in map.kf_kps]
+    first = np.nonzero(np.asarray(map.kf_id) == 0)[0]
+    i = map.info
+    return dict(kf_off=kf_off, octave=octave, slots=slots, mp_bad=mp_bad, obs_off=obs_off, obs_gkp=obs_gkp, where=where,
+                kf_bad=map.kf_bad.astype(np.uint8), kp_xy=np.ascontiguousarray(np.concatenate(xy)),
+                kf_Tcw=np.ascontiguousarray(map.Tcw, np.float32).reshape(-1, 16),
+                mp_pos=np.ascontiguousarray(map.mps["pos"], np.float32).reshape(-1, 3),
+                inv_sigma2=inv_level_sigma2(i.nlevels, i.scale_factor), cam=np.asarray([i.fx, i.fy, i.cx, i.cy], np.float32),
+                kf0=int(first[0]) if len(first) else -1)
+
+
+def lba_local_keyframes(map, cur: int) -> list:
+    """lLocalKeyFrames (Optimizer.cc:1520-1530): the current keyframe, then its
+    ordered covisibles that are not bad."""
+    return [int(cur)] + [int(k) for k in map.ordered[int(cur)] if not map.kf_bad[int(k)]]
+
+
+def _lba_struct(t: dict, arrays: dict) -> LBATables:
+    """The gf_lba_tables of the (host or device) ``arrays``, after checking the
+    host-side lengths of ``t`` against each other."""
+    n = dict(nkf=len(t["kf_off"]) - 1, nkp=len(t["octave"]), nmp=len(t["mp_bad"]), nobs=len(t["obs_gkp"]),
+             nlevels=len(t["inv_sigma2"]))
+    if n["nkf"] < 0 or len(np.asarray(t["cam"]).reshape(-1)) != 4:
+        raise GFError(-1, "table lengths disagree")
+    for name, _, per, size in _LBA_TABLES:
+        want = (n[size[:-1]] + 1 if size.endswith("+") else n[size]) * per
+        if np.asarray(t[name]).size != want:
+            raise GFError(-1, f"table lengths disagree: {name} has {np.asarray(t[name]).size} elements, not {want}")
+    q = LBATables(n["nkf"], n["nkp"], n["nmp"], n["nobs"], n["nlevels"], int(t["kf0"]),
+                  *[ptr(arrays[name]) if _n_el(arrays[name]) else None for name, *_ in _LBA_TABLES])
+    q.cam[:] = [float(x) for x in np.asarray(t["cam"], np.float32).reshape(4)]
+    return q
+
+
+def _n_el(a) -> int:
+    return int(a.numel()) if hasattr(a, "numel") else int(a.size)
+
+
+def _lba_cut(bufs: dict, counts) -> dict:
+    """The compact problem of the bound-sized output buffers (host arrays)."""
+    g = dict(nkf=int(counts[0]), npts=int(counts[1]), nedges=int(counts[2]))
+    for name, _, per, which in _LBA_OUT:
+        a = bufs[name][:int(counts[which]) * per]
+        g[name] = a.reshape(-1, per).copy() if per > 1 else a.copy()
+    return g
+
+
+def lba_graph_arrays(tables: dict, local, ctx=None) -> dict:
+    """``gf_lba_graph`` on host arrays (Optimizer.cc:1517-1675): ``tables`` as
+    :func:`lba_tables` gives them, ``local`` as :func:`lba_local_keyframes`.
+    -> dict: ``nkf`` / ``npts`` / ``nedges``, the gf_ba_problem arrays
+    (``kf_Tcw``, ``kf_kind``, ``kf_cam``, ``pt_pos``, ``edge_pt``, ``edge_kf``,
+    ``edge_z``, ``edge_inv_sigma2``), ``prob_kf`` / ``prob_pt`` (the map index
+    of every problem keyframe / point) and ``edge_gkp`` (the global keypoint
+    index of every edge)."""
+    ctx = ctx or default_context()
+    host = {name: np.ascontiguousarray(tables[name], dt).reshape(-1) for name, dt, _, _ in _LBA_TABLES}
+    q = _lba_struct(tables, host)
+    local = np.ascontiguousarray(local, np.int32).reshape(-1)
+    bound = (max(q.nkf, 1), max(q.nmp, 1), max(q.nobs, 1))
+    bufs = {name: np.zeros(bound[which] * per, dt) for name, dt, per, which in _LBA_OUT}
+    counts = np.zeros(3, np.int32)
+    out = LBAGraphOut(ptr(counts), *[ptr(bufs[name]) for name, *_ in _LBA_OUT])
+    check(lib().gf_lba_graph(ctx.handle, ctypes.byref(q), len(local), ptr(local), ctypes.byref(out)))
+    return _lba_cut(bufs, counts)
+
+
+class _LBATables:
+    """The tables of :func:`lba_tables` for one LocalBundleAdjustment, resident
+    on the device (uploaded once) with the bound-sized output buffers of
+    ``gf_lba_graph_dev`` next to them."""
+
+    def __init__(self, map, ctx):
+        import torch
+
+        self.ctx, self.torch = ctx, torch
+        self.t = lba_tables(map)
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.d = {name: self._t(np.ascontiguousarray(self.t[name], dt).reshape(-1)) for name, dt, _, _ in _LBA_TABLES}
+        self.q = _lba_struct(self.t, self.d)
+        bound = (max(self.q.nkf, 1), max(self.q.nmp, 1), max(self.q.nobs, 1))
+        tdt = {np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}
+        self.o = {name: torch.empty(bound[which] * per, dtype=tdt[dt], device=self.dev)
+                  for name, dt, per, which in _LBA_OUT}
+        self.counts = torch.zeros(3, dtype=torch.int32, device=self.dev)
+        self.out = LBAGraphOut(ptr(self.counts), *[ptr(self.o[name]) for name, *_ in _LBA_OUT])
+        torch.cuda.current_stream().synchronize()  # the uploads ran on torch's stream
+
+    def _t(self, a):
+        return self.torch.from_numpy(a).to(self.dev)
+
+    def launch(self, local):
+        """The assembly enqueued on the context's stream and waited for."""
+        local = np.ascontiguousarray(local, np.int32).reshape(-1)
+        check(lib().gf_lba_graph_dev(self.ctx.handle, ctypes.byref(self.q), len(local), ptr(local),
+                                     ctypes.byref(self.out), self.ctx.stream))
+        self.ctx.sync()
+
+    def download(self) -> dict:
+        """The compact problem: the counts first, then that much of every buffer."""
+        counts = self.counts.cpu().numpy()
+        return _lba_cut({name: self.o[name][:int(counts[which]) * per].cpu().numpy()
+                         for name, _, per, which in _LBA_OUT}, counts)
+
+
+def local_bundle_adjustment(map, cur: int, stop_flag=None, ctx=None, assembler=None, solver=None) -> dict:
+    """Optimizer::LocalBundleAdjustment(pKF, pbStopFlag) (src/Optimizer.cc:
+    1515-1764; LocalMapping.cc:108) on a LoopMap for the current keyframe
+    ``cur``.
+
+    Tables: :func:`lba_tables`, built once and uploaded once
+    (:class:`_LBATables`). Assembly (:1517-1675): one ``gf_lba_graph_dev`` call
+    for the local list of :func:`lba_local_keyframes`; the compact problem is
+    downloaded. Solve: ``gf_local_ba_stop`` (``optimizer.local_bundle_adjustment``),
+    ``stop_flag`` (a ``ctypes.c_uint8``) polled as mbAbortBA; without edges
+    nothing is solved. A local point none of whose observers is alive is a
+    vertex without edges: the solver accepts it and leaves it where it is.
+
+    Write-back (:1681-1763) on the map, in the reference's order: the first
+    erasure loop walks the edges in order, skips an edge whose point is bad by
+    then, and on flag 1 calls ``erase_map_point_match(kf, obs[p][kf])`` then
+    ``erase_observation(p, kf)``, which may turn the point bad and clear its
+    other slots; the second loop does the same for flag 2; then ``set_pose`` of
+    every keyframe of kind 0 or 1, the final position of every local point
+    (bad ones included: SetWorldPos has no bad test) and
+    ``update_normal_and_depth_batch`` of the local points.
+
+    Two departures (docs/ORACLE_ASSUMPTIONS.md A31, A32). (a) The reference's
+    first loop skips an outlier edge whose point an earlier erasure of the same
+    loop turned bad, so that edge stays in optimize(10); the solver drops every
+    first-round outlier. The map surgery is the same (a bad point has no
+    observations left), only the second solve differs; ``stale_outliers``
+    counts those edges. (b) The intermediate recover (:1700-1717) is not run:
+    all it writes is written again at :1745-1763, except ``normal`` /
+    ``min_dist`` / ``max_dist`` of a point that turns bad in the second loop,
+    which the reference leaves at values from poses the solver does not
+    expose; here they are left untouched.
+
+    assembler(tables, local) / solver(problem): callables used instead of the
+    device (the CPU tests inject the restatement's graph and the oracle's
+    solver); with an assembler the final update runs on the host too.
+
+    -> report dict: ``local_kfs`` (list order), ``fixed_kfs`` (index order),
+    ``npts``, ``nedges``, ``iterations``, ``erased`` (edges erased per round),
+    ``points_bad``, ``bad_round2`` (those of them from the second loop),
+    ``stale_outliers``, ``graph`` (the assembled problem), ``flags`` /
+    ``kf_Tcw`` / ``pt_pos`` (the solver's result, when it ran) and ``times``: seconds spent in tables, assembly, download, solve, write-back
+    and update."""
+    import time
+
+    from .optimizer import local_bundle_adjustment as solve_window
+
+    cur = int(cur)
+    local = lba_local_keyframes(map, cur)
+    if sum(1 for k in local if map.kf_id[k] != 0) > MAX_LOCAL_BA_KEYFRAMES:
+        raise GFError(-1, "more than 32 local (non-fixed) keyframes")
+    times = dict(tables=0.0, assembly=0.0, download=0.0, solve=0.0, writeback=0.0, update=0.0)
+    t = [time.perf_counter()]
+
+    def lap(name):
+        t.append(time.perf_counter())
+        times[name] += t[-1] - t[-2]
+
+    if assembler is None:
+        ctx = ctx or default_context()
+        tables = _LBATables(map, ctx)
+        lap("tables")
+        tables.launch(local)
+        lap("assembly")
+        g = tables.download()
+        lap("download")
+    else:
+        tables = lba_tables(map)
+        lap("tables")
+        g = assembler(tables, local)
+        lap("assembly")
+    rep = dict(local_kfs=local, fixed_kfs=[int(k) for k, kind in zip(g["prob_kf"], g["kf_kind"]) if kind == 2],
+               npts=g["npts"], nedges=g["nedges"], iterations=(-1, -1), erased=[0, 0], points_bad=[], bad_round2=[],
+               stale_outliers=0, graph=g, flags=np.zeros(0, np.uint8), times=times)
+    if not g["nedges"]:
+        return rep
+    if solver is None:
+        T, X, flags, its = solve_window(g, ctx, stop_flag)
+    else:
+        T, X, flags, its = solver(g)
+    lap("solve")
+    rep["iterations"], rep["flags"], rep["kf_Tcw"], rep["pt_pos"] = tuple(int(i) for i in its), flags, T, X
+    edge_p = g["prob_pt"][g["edge_pt"]]
+    edge_k = g["prob_kf"][g["edge_kf"]]
+    for rnd in (1, 2):
+        for e in np.nonzero(flags == rnd)[0]:
+            p, k = int(edge_p[e]), int(edge_k[e])
+            if map.mp_bad[p]:
+                rep["stale_outliers"] += rnd == 1
+                continue
+            idx = map.obs[p].get(k, -1)  # GetIndexInKeyFrame
+            if idx >= 0:
+                map.erase_map_point_match(k, idx)
+            if map.erase_observation(p, k):
+                rep["points_bad"].append(p)
+                if rnd == 2:
+                    rep["bad_round2"].append(p)
+            rep["erased"][rnd - 1] += 1
+    for q, (k, kind) in enumerate(zip(g["prob_kf"], g["kf_kind"])):
+        if kind != 2:
+            map.set_pose(int(k), T[q])
+    map.mps["pos"][g["prob_pt"]] = np.asarray(X, np.float32).reshape(-1, 3)
+    lap("writeback")
+    ids = [int(p) for p in g["prob_pt"]]
+    if assembler is None:
+        map.update_normal_and_depth_batch(ids, ctx)
+    else:
+        map.update_normal_and_depth(ids)
+    lap("update")
+    return rep

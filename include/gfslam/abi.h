@@ -725,6 +725,83 @@ int gf_keyframe_culling_counts_dev(gf_ctx* ctx, int nkf, int nkp, const int32_t*
                                    const int32_t* d_obs_gkp, int nobs, int ncand, const int32_t* d_cand,
                                    int32_t* d_counts, uint8_t* d_flags, void* stream);
 
+/* The graph assembly of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:
+ * 1517-1675) over flat tables of the whole map: the five tables of
+ * gf_keyframe_culling_counts (kf_off, octave, slots, mp_bad, obs_off /
+ * obs_gkp, -1 = an erased observation) plus kf_bad[nkf], kp_xy[nkp x 2] =
+ * GetKeyPointUn(i).pt keyframe-major like octave, inv_sigma2[nlevels] =
+ * GetInvSigma2(level), kf_Tcw[nkf x 16], mp_pos[nmp x 3], one camera cam =
+ * {fx, fy, cx, cy}, and kf0 = the index of the keyframe with mnId 0 (-1: not
+ * in the map). Keyframe indices are in mnId order. */
+typedef struct gf_lba_tables {
+    int32_t nkf, nkp, nmp, nobs, nlevels, kf0;
+    const int32_t* kf_off;   /* nkf + 1 */
+    const uint8_t* octave;   /* nkp */
+    const int32_t* slots;    /* nkp */
+    const uint8_t* kf_bad;   /* nkf */
+    const float* kp_xy;      /* nkp x 2 */
+    const float* kf_Tcw;     /* nkf x 16 */
+    const uint8_t* mp_bad;   /* nmp */
+    const float* mp_pos;     /* nmp x 3 */
+    const int32_t* obs_off;  /* nmp + 1 */
+    const int32_t* obs_gkp;  /* nobs */
+    const float* inv_sigma2; /* nlevels */
+    float cam[4];
+} gf_lba_tables;
+
+/* The assembled gf_ba_problem and what the write-back needs. Every buffer is
+ * sized by its safe bound (nkf keyframes, nmp points, nobs edges of the
+ * tables); counts = {nkf, npts, nedges} of the problem. prob_kf / prob_pt:
+ * the map index of every problem keyframe / point; edge_gkp: the global
+ * keypoint index kf_off[kf] + idx of every edge. */
+typedef struct gf_lba_graph_out {
+    int32_t* counts;        /* 3 */
+    int32_t* prob_kf;       /* nkf */
+    uint8_t* kf_kind;       /* nkf */
+    float* kf_Tcw;          /* nkf x 16 */
+    float* kf_cam;          /* nkf x 4 */
+    int32_t* prob_pt;       /* nmp */
+    float* pt_pos;          /* nmp x 3 */
+    int32_t* edge_pt;       /* nobs */
+    int32_t* edge_kf;       /* nobs */
+    float* edge_z;          /* nobs x 2 */
+    float* edge_inv_sigma2; /* nobs */
+    int32_t* edge_gkp;      /* nobs */
+} gf_lba_graph_out;
+
+/* Optimizer.cc:1517-1675 on host arrays, synchronous. local[0] is the current
+ * keyframe, local[1..nlocal) its GetVectorCovisibleKeyFrames() in list order
+ * with the bad ones left out (:1523-1530). The problem, in the orders
+ * gf_ba_problem demands:
+ *   keyframes in index order: the local list (kind 0, or 1 for kf0) united
+ *     with the fixed cameras (kind 2): the observers of a local point that are
+ *     neither local nor bad (:1552-1566);
+ *   points in id order: every point with 0 <= p < nmp and !mp_bad[p] found in
+ *     a slot of a local keyframe (:1534-1548);
+ *   edges: the points in lLocalMapPoints order (first occurrence when the
+ *     local keyframes are walked in list order and their slots in index
+ *     order), each point's row in row order, -1 entries and observers with
+ *     kf_bad skipped (:1644).
+ * GF_ERR_ARG, nothing written, for: kf_off / obs_off that do not start at 0,
+ * decrease or do not end at nkp / nobs, a keyframe above 4096 keypoints, an
+ * octave >= nlevels, nlevels outside [1, 16], an observation entry outside
+ * [-1, nkp), kf0 outside [-1, nkf), an empty local list, a local index
+ * outside [0, nkf), a repeat, or more than 32 local keyframes of kind 0 (the
+ * solver's limit). */
+int gf_lba_graph(gf_ctx* ctx, const gf_lba_tables* tables, int nlocal, const int32_t* local,
+                 const gf_lba_graph_out* out);
+/* Device family (Optimizer.cc:1517-1675): the pointers of d_tables and d_out
+ * are device pointers (the two structs and local are host memory, read at the
+ * call), enqueued on stream without synchronising; the entry clears its own
+ * workspace. kf_Tcw, kp_xy and the float outputs are read and written as
+ * 16- and 8-byte vectors: device allocations as they come (hipMalloc, a
+ * tensor's storage) are aligned enough. The local list is checked as above; the tables are not read on
+ * the host: a slot outside [0, nmp), a row outside [0, nobs) and an entry
+ * outside [0, nkp) are skipped, a keyframe is walked up to 4096 slots, an
+ * octave is clamped to nlevels - 1. */
+int gf_lba_graph_dev(gf_ctx* ctx, const gf_lba_tables* d_tables, int nlocal, const int32_t* local,
+                     const gf_lba_graph_out* d_out, void* stream);
+
 /* ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, ...) (src/ORBmatcher.cc:
  * 1426-1588): keypoints of a (pKF1) and b (pKF2) without a map point
  * (mp < 0) that share a FeatureVector node; best distance <= TH_LOW, the
