@@ -121,6 +121,14 @@ all: $(LBAMAPREF)
 $(LBAMAPREF): tests/helpers/lbamap_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of KeyFrame::UpdateConnections / AddConnection and
+# of the index state of LocalMapping::ProcessNewKeyFrame
+# (tests/test_covis_cpu.py, tests/test_covis_gpu.py), same flags
+COVISREF = tests/helpers/libcovisref.so
+all: $(COVISREF)
+$(COVISREF): tests/helpers/covis_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

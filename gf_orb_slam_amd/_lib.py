@@ -151,6 +151,8 @@ _PROTOS = {
     "gf_update_normal_and_depth_dev": [_P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "gf_keyframe_culling_counts": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P],
     "gf_keyframe_culling_counts_dev": [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "gf_update_connections": [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "gf_update_connections_dev": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "gf_lba_graph": [_P, _P, _I, _P, _P],
     "gf_lba_graph_dev": [_P, _P, _I, _P, _P, _P],
     "gf_search_for_triangulation": [_P, _I, _P, _P, _P, _P, _I, _P, _P],

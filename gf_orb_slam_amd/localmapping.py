@@ -21,6 +21,13 @@ LocalBundleAdjustment (src/Optimizer.cc:1515-1764) assembles its graph on the
 device (``gf_lba_graph_dev``: the gather, the vertices and the edges from flat
 tables of the map), solves it with ``gf_local_ba_stop`` and applies the outlier
 erasure and the write-back of :1681-1763 here on the host.
+
+ProcessNewKeyFrame (src/LocalMapping.cc:163-211) computes the keyframe's BoW
+vectors, associates its points on the host and runs KeyFrame::UpdateConnections
+(src/KeyFrame.cc:332-421) with the counting and ordering on the device
+(``gf_update_connections_dev``: any number of keyframes in one launch) and the
+graph updates on the host (``LoopMap.apply_connections``). :class:`LocalMapper`
+strings the stages together as the body of ``LocalMapping::Run`` does.
 """
 from __future__ import annotations
 
@@ -29,7 +36,7 @@ import ctypes
 import numpy as np
 
 from ._lib import GFError, check, lib, ptr
-from .bow import BowSide
+from .bow import BowSide, FeatureVector
 from .orb import default_context
 
 MAX_NEIGHBOURS = 20
@@ -340,6 +347,233 @@ def keyframe_culling(map, cur: int, db=None, ctx=None, counter=None) -> dict:
     lap("walk")
     rep["launches"] = tables.launches
     return rep
+
+
+# ------------------------------------------------ ProcessNewKeyFrame / UpdateConnections
+def update_connections_counts(kf_off, slots, mp_bad, obs_off, obs_gkp, query, ctx=None):
+    """``gf_update_connections`` on host arrays (the counting and ordering of
+    KeyFrame.cc:332-403 for every query keyframe in one launch) -> (weights
+    [nq, nkf], n_ordered [nq], ordered_kf [nq, nkf], ordered_w [nq, nkf]), all
+    int32; the ordered rows hold -1 / 0 past n_ordered."""
+    ctx = ctx or default_context()
+    c = np.ascontiguousarray
+    kf_off, slots, obs_off, obs_gkp, query = (c(a, np.int32).reshape(-1) for a in (kf_off, slots, obs_off, obs_gkp, query))
+    mp_bad = c(mp_bad, np.uint8).reshape(-1)
+    if len(kf_off) < 1 or len(obs_off) != len(mp_bad) + 1:
+        raise GFError(-1, "table lengths disagree")
+    nkf, nq = len(kf_off) - 1, len(query)
+    if (nkf and kf_off[-1] != len(slots)) or obs_off[-1] != len(obs_gkp):
+        raise GFError(-1, "table lengths disagree")
+    weights, n_ordered = np.zeros((nq, nkf), np.int32), np.zeros(nq, np.int32)
+    ordered_kf, ordered_w = np.full((nq, nkf), -1, np.int32), np.zeros((nq, nkf), np.int32)
+    check(lib().gf_update_connections(ctx.handle, nkf, ptr(kf_off), ptr(slots), len(mp_bad), ptr(mp_bad), ptr(obs_off),
+                                      ptr(obs_gkp), nq, ptr(query), ptr(weights) if nkf else None, ptr(n_ordered),
+                                      ptr(ordered_kf) if nkf else None, ptr(ordered_w) if nkf else None))
+    return weights, n_ordered, ordered_kf, ordered_w
+
+
+class _CovisTables:
+    """The tables of :func:`culling_tables` that UpdateConnections reads
+    (``kf_off``, ``slots``, ``mp_bad``, ``obs_off``, ``obs_gkp``) for one
+    ``LoopMap.connections_counts``, uploaded once unless a host ``counter`` is
+    injected."""
+
+    def __init__(self, map, ctx=None, counter=None):
+        self.counter = counter
+        self.kf_off, _, self.slots, self.mp_bad, self.obs_off, self.obs_gkp, _ = culling_tables(map)
+        self.nkf = map.nkf
+        if counter is None:
+            import torch
+
+            self.ctx, self.torch = ctx or default_context(), torch
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+            self.d = [self._t(a) for a in (self.kf_off, self.slots, self.mp_bad, self.obs_off, self.obs_gkp)]
+            torch.cuda.current_stream().synchronize()
+
+    def _t(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def count(self, kfs):
+        """One launch over the query keyframes -> (weights [nq, nkf], per
+        query ``(ordered keyframes, their weights)`` as lists)."""
+        query = np.ascontiguousarray([int(k) for k in kfs], np.int32)
+        nq, nkf = len(query), self.nkf
+        if not nq or not nkf:
+            return np.zeros((nq, nkf), np.int32), [([], []) for _ in range(nq)]
+        if self.counter is not None:
+            w, n, ok, ow = self.counter(self.kf_off, self.slots, self.mp_bad, self.obs_off, self.obs_gkp, query)
+        else:
+            torch = self.torch
+            d_query = self._t(query)
+            d_out = torch.empty((3 * nkf + 1) * nq, dtype=torch.int32, device=self.dev)  # weights | kf | w | n
+            torch.cuda.current_stream().synchronize()  # the uploads ran on torch's stream
+            d, row = self.d, nq * nkf
+            check(lib().gf_update_connections_dev(self.ctx.handle, nkf, len(self.slots), ptr(d[0]), ptr(d[1]),
+                                                  len(self.mp_bad), ptr(d[2]), ptr(d[3]), ptr(d[4]), len(self.obs_gkp),
+                                                  nq, ptr(d_query), ptr(d_out), ptr(d_out[3 * row:]),
+                                                  ptr(d_out[row:]), ptr(d_out[2 * row:]), self.ctx.stream))
+            self.ctx.sync()
+            out = d_out.cpu().numpy()
+            w, ok, ow, n = (out[:row].reshape(nq, nkf), out[row:2 * row].reshape(nq, nkf),
+                            out[2 * row:3 * row].reshape(nq, nkf), out[3 * row:])
+        w, n, ok, ow = (np.asarray(a, np.int32) for a in (w, n, ok, ow))
+        return w.reshape(nq, nkf), [(ok.reshape(nq, nkf)[i, :n[i]].tolist(), ow.reshape(nq, nkf)[i, :n[i]].tolist())
+                                    for i in range(nq)]
+
+
+def process_new_keyframe(map, cur: int, voc, recent: list, levelsup: int = 4, ctx=None, counter=None) -> dict:
+    """LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:163-211) on a
+    LoopMap for the keyframe ``cur``, already appended with
+    ``LoopMap.add_keyframe``.
+
+    ComputeBoW (KeyFrame.cc:56-65): only when ``map.kf_bow[cur]`` or
+    ``map.kf_fv[cur]`` is empty; ``voc`` is an ``ORBVocabulary`` (its
+    ``transform``) or a callable ``(descriptors, levelsup) -> (words, values,
+    FeatureVector or (nodes, start, feats))``; both results are stored. The
+    first keyframe (mnId 0) returns after it (:172-173).
+
+    mnId > 1 (:177-192): the slot table is copied once and walked in slot
+    order; every non-NULL, non-bad point gets ``add_observation(p, cur, i)``, so
+    a point in two slots ends with the later one. The reference then calls
+    UpdateNormalAndDepth and ComputeDistinctiveDescriptors on the point inside
+    the loop; here both run once over the distinct ids after it
+    (``update_normal_and_depth_batch``, ``compute_distinctive_descriptors``).
+    That is the same: each reads only its own point's observations, the
+    keyframes' descriptors and poses and the point's position, and writes only
+    its own point's normal, distance bounds and descriptor, which the other
+    call and every other point's calls never read. A point's observations change
+    inside the loop only through its own ``add_observation``, so they are
+    final after its last slot, and the calls the reference makes at an earlier
+    slot of the same point are recomputed from scratch at the later one. No
+    pose and no keyframe descriptor changes in between.
+
+    mnId 1 (:194-204): every non-NULL slot point, bad ones included (the test
+    is on the pointer only), is appended to ``recent``
+    (mlpRecentAddedMapPoints).
+
+    UpdateConnections (:207): one ``gf_update_connections_dev`` launch for
+    ``cur`` (``counter``: a host callable instead, as in
+    ``LoopMap.connections_counts``), then ``map.apply_connections``.
+
+    -> report dict: ``associated`` (the ids given an observation, in slot
+    order), ``recent_added``, ``n_ordered``, ``parent`` and ``times``: seconds
+    spent in bow, association, tables (build and upload), launch (and
+    download) and apply."""
+    import time
+
+    cur = int(cur)
+    times = dict(bow=0.0, association=0.0, tables=0.0, launch=0.0, apply=0.0)
+    rep = dict(associated=[], recent_added=[], n_ordered=0, parent=int(map.parent[cur]), times=times)
+    t = [time.perf_counter()]
+
+    def lap(name):
+        t.append(time.perf_counter())
+        times[name] += t[-1] - t[-2]
+
+    if map.kf_bow[cur] is None or map.kf_fv[cur] is None:
+        transform = voc.transform if hasattr(voc, "transform") else voc
+        words, values, fv = transform(map.kf_desc[cur], levelsup)
+        map.kf_bow[cur] = (words, values)
+        map.kf_fv[cur] = fv if isinstance(fv, FeatureVector) else FeatureVector(*fv)
+    lap("bow")
+    cur_id = int(map.kf_id[cur])
+    if cur_id == 0:
+        return rep
+    pts = map.slots[cur].copy()  # vpMapPointMatches (:176), taken once
+    if cur_id > 1:
+        for i, p in enumerate(pts):
+            p = int(p)
+            if p < 0 or map.mp_bad[p]:
+                continue
+            map.add_observation(p, cur, i)
+            rep["associated"].append(p)
+        ids = list(dict.fromkeys(rep["associated"]))
+        if counter is None:
+            map.update_normal_and_depth_batch(ids, ctx)
+        else:
+            map.update_normal_and_depth(ids)
+        map.compute_distinctive_descriptors(ids)
+    else:
+        rep["recent_added"] = [int(p) for p in pts if p >= 0]
+        recent.extend(rep["recent_added"])
+    lap("association")
+    tables = _CovisTables(map, ctx, counter)
+    lap("tables")
+    weights, ordered = tables.count([cur])
+    lap("launch")
+    map.apply_connections(cur, weights[0], *ordered[0])
+    lap("apply")
+    rep["n_ordered"], rep["parent"] = len(ordered[0][0]), int(map.parent[cur])
+    return rep
+
+
+class LocalMapper:
+    """The body of ``LocalMapping::Run`` (src/LocalMapping.cc:49-129) for one
+    keyframe at a time on a LoopMap, without the queue and the thread: the
+    caller inserts a keyframe and steps it through the stages in the
+    reference's order. Holds the map, the vocabulary, mlpRecentAddedMapPoints
+    (``recent``) and the context, and optionally the keyframe database ``db``
+    (``loopdetect.KeyFrameDatabase``, told of culled keyframes) and the loop
+    ``detector`` (``loopdetect.LoopDetector``, kept for the caller: the keyframe
+    a step returns in ``to_loop_closer`` is what mpLoopCloser->InsertKeyFrame
+    would receive, and calling the detector with it is the caller's business).
+
+    counter / assembler / solver: host callables handed to the stages that
+    take them (``process_new_keyframe``, ``keyframe_culling``;
+    ``local_bundle_adjustment``); stages: a dict replacing stage functions by
+    name (the CPU tests record the order with it)."""
+
+    STAGES = ("process_new_keyframe", "map_point_culling", "create_new_map_points", "search_in_neighbors",
+              "local_bundle_adjustment", "keyframe_culling")
+
+    def __init__(self, map, voc, ctx=None, db=None, detector=None, levelsup=4, counter=None, cull_counter=None,
+                 assembler=None, solver=None, stages=None):
+        self.map, self.voc, self.ctx, self.db, self.detector = map, voc, ctx, db, detector
+        self.levelsup, self.recent = levelsup, []
+        self.counter, self.cull_counter, self.assembler, self.solver = counter, cull_counter, assembler, solver
+        self.stages = dict(process_new_keyframe=process_new_keyframe, map_point_culling=map_point_culling,
+                           create_new_map_points=create_new_map_points, search_in_neighbors=search_in_neighbors,
+                           local_bundle_adjustment=local_bundle_adjustment, keyframe_culling=keyframe_culling)
+        self.stages.update(stages or {})
+
+    def insert_keyframe(self, kps, desc, slots, Tcw, kf_id=None) -> int:
+        """What tracking hands over (LocalMapping::InsertKeyFrame after ``new
+        KeyFrame``): ``map.add_keyframe`` -> the keyframe's index."""
+        return self.map.add_keyframe(kps, desc, slots, Tcw, kf_id)
+
+    def step(self, cur: int, abort_ba: bool = False, stop_flag=None) -> dict:
+        """One pass of the loop body for keyframe ``cur`` (:68-124):
+        ProcessNewKeyFrame, MapPointCulling, CreateNewMapPoints (with
+        ``map.kf_fv``), SearchInNeighbors and, unless ``abort_ba`` (mbAbortBA /
+        stopRequested, :100), LocalBundleAdjustment (``stop_flag`` polled inside)
+        and KeyFrameCulling. -> report dict: per stage run ``dict(report=the
+        stage's own, seconds=host clock)``; ``order``: the stages run;
+        ``to_loop_closer``: ``cur`` (:124)."""
+        import time
+
+        cur, m, s = int(cur), self.map, self.stages
+        rep = dict(order=[])
+
+        def run(name, fn):
+            t0 = time.perf_counter()
+            out = fn()
+            rep[name] = dict(report=out, seconds=time.perf_counter() - t0)
+            rep["order"].append(name)
+            return out
+
+        run("process_new_keyframe", lambda: s["process_new_keyframe"](m, cur, self.voc, self.recent, self.levelsup,
+                                                                      ctx=self.ctx, counter=self.counter))
+        self.recent[:] = run("map_point_culling", lambda: s["map_point_culling"](m, self.recent, cur))
+        ids, _ = run("create_new_map_points", lambda: s["create_new_map_points"](m, cur, m.kf_fv, ctx=self.ctx))
+        self.recent.extend(ids)  # mlpRecentAddedMapPoints.push_back (:406)
+        run("search_in_neighbors", lambda: s["search_in_neighbors"](m, cur, ctx=self.ctx))
+        if not abort_ba:
+            run("local_bundle_adjustment", lambda: s["local_bundle_adjustment"](
+                m, cur, stop_flag=stop_flag, ctx=self.ctx, assembler=self.assembler, solver=self.solver))
+            run("keyframe_culling", lambda: s["keyframe_culling"](m, cur, db=self.db, ctx=self.ctx,
+                                                                  counter=self.cull_counter))
+        rep["to_loop_closer"] = cur
+        return rep
 
 
 class _DeviceMap:

@@ -1,8 +1,8 @@
 """What ``LoopClosing::CorrectLoop`` reads and writes of ``Map`` / ``KeyFrame``
 / ``MapPoint``, as index arrays.
 
-A keyframe is an index into the lists given at construction, a map point an
-index into ``mps``. The slot tables (``KeyFrame::mvpMapPoints``) and the
+A keyframe is an index into the lists given at construction and grown by
+``add_keyframe``, a map point an index into ``mps``. The slot tables (``KeyFrame::mvpMapPoints``) and the
 observation maps (``MapPoint::mObservations``) are separate state, as in the
 reference: ``AddObservation`` overwrites, and nothing here assumes that the two
 agree or that a point sits in one slot per keyframe. Pointer-ordered containers
@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._lib import GFError
 from .matcher import MAP_POINT_DTYPE
 from .orb import KEYPOINT_DTYPE
 
@@ -79,6 +80,51 @@ class LoopMap:
         # mbNotErase / mbToBeErased (KeyFrame.cc:474-508)
         self.not_erase = np.zeros(self.nkf, bool)
         self.to_be_erased = np.zeros(self.nkf, bool)
+        # mBowVec as (words, values) / mFeatVec as a FeatureVector, None until ComputeBoW ran
+        self.kf_bow = [None] * self.nkf
+        self.kf_fv = [None] * self.nkf
+
+    # ------------------------------------------------------------ Map
+    def add_keyframe(self, kps, desc, slots, Tcw, kf_id=None) -> int:
+        """``new KeyFrame(frame, pMap, pKFDB)`` + ``Map::AddKeyFrame``
+        (KeyFrame.cc:30-54, Map.cc:33-39): a keyframe with the keypoints,
+        descriptors, slot table (what tracking matched) and pose given, not
+        bad, without connections, parent or BoW vectors, first connection
+        pending. kf_id: its mnId, default the last one + 1; it must stay
+        strictly increasing. No observation is added: the observation maps do
+        not know the keyframe until ProcessNewKeyFrame, as in the reference.
+        Returns its index."""
+        kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1).copy()
+        if not len(kps) == len(desc) == len(slots):
+            raise GFError(-1, "keypoints, descriptors and slots: one row per keypoint")
+        if len(slots) and (slots.min() < -1 or slots.max() >= len(self.mps)):
+            raise GFError(-1, "a slot names a point outside the map")
+        last = int(self.kf_id[-1]) if self.nkf else -1
+        kf_id = last + 1 if kf_id is None else int(kf_id)
+        if kf_id <= last:
+            raise GFError(-1, f"mnId {kf_id} does not follow {last}")
+        k = self.nkf
+        self.kf_kps.append(kps)
+        self.kf_desc.append(desc)
+        self.slots.append(slots)
+        self.kf_bad = np.append(self.kf_bad, False)
+        self.Tcw = np.concatenate([self.Tcw.reshape(-1, 4, 4), np.asarray(Tcw, np.float32).reshape(1, 4, 4)])
+        self.kf_id = np.append(self.kf_id, np.int32(kf_id))
+        self.fuse_target_for = np.append(self.fuse_target_for, np.int64(-1))
+        self.weights.append({})
+        self.ordered.append([])
+        self.ordered_w.append([])
+        self.parent.append(-1)
+        self.first_connection.append(True)
+        self.loop_edges.append([])
+        self.not_erase = np.append(self.not_erase, False)
+        self.to_be_erased = np.append(self.to_be_erased, False)
+        self.kf_bow.append(None)
+        self.kf_fv.append(None)
+        self.nkf = k + 1
+        return k
 
     # ------------------------------------------------------------ MapPoint
     def is_in_keyframe(self, p: int, kf: int) -> bool:
@@ -442,6 +488,59 @@ class LoopMap:
         if self.first_connection[kf] and kf != 0:
             self.parent[kf] = self.ordered[kf][0]
             self.first_connection[kf] = False
+
+    def connections_counts(self, kfs, ctx=None, counter=None):
+        """The counting and ordering of UpdateConnections (KeyFrame.cc:332-403)
+        for every keyframe of ``kfs`` in one ``gf_update_connections_dev``
+        launch over the flat tables of the map as it stands
+        (``localmapping.culling_tables``). It reads slot tables, observation
+        maps and bad flags only, none of which UpdateConnections writes, so any
+        number of keyframes can be counted before the first is applied.
+        counter: a callable with the signature of
+        ``localmapping.update_connections_counts`` used instead of the device
+        (the CPU tests inject the restatement's).
+        -> (weights [len(kfs), nkf] int32, 0 = not in the counter; per keyframe
+        ``(ordered keyframes, their weights)`` as lists)."""
+        from .localmapping import _CovisTables
+
+        return _CovisTables(self, ctx, counter).count(kfs)
+
+    def apply_connections(self, kf: int, weights_row, ordered_kf, ordered_w) -> None:
+        """The rest of UpdateConnections (KeyFrame.cc:365-418) from one row of
+        :meth:`connections_counts`: nothing when the counter is empty (:365);
+        otherwise AddConnection(kf, w) on every listed keyframe (:386, :393),
+        the keyframe's weight map (every counted keyframe), ordered list and
+        ordered weights (:409-411), and on its first connection the head of
+        the list as parent (:413-418). The first-connection test is that of
+        :meth:`update_connections`, so that the two stay equal field by field:
+        the map's first keyframe never gets a parent. Keyframe ids increase
+        with the index, so mnId 0 (the reference's test) can sit nowhere else;
+        the two tests differ only on a map whose first keyframe has another id
+        (docs/ORACLE_ASSUMPTIONS.md A26). The listed keyframes are distinct, so
+        the order of the AddConnection calls (here list order, there index
+        order) changes nothing."""
+        kf = int(kf)
+        ordered_kf, ordered_w = [int(k) for k in ordered_kf], [int(w) for w in ordered_w]
+        if not ordered_kf:
+            return
+        for k, w in zip(ordered_kf, ordered_w):
+            self.add_connection(k, kf, w)
+        row = np.asarray(weights_row)
+        self.weights[kf] = {int(k): int(row[k]) for k in np.nonzero(row > 0)[0]}
+        self.ordered[kf], self.ordered_w[kf] = ordered_kf, ordered_w
+        if self.first_connection[kf] and kf != 0:
+            self.parent[kf] = ordered_kf[0]
+            self.first_connection[kf] = False
+
+    def update_connections_batch(self, kfs, ctx=None, counter=None) -> None:
+        """:meth:`update_connections` of every keyframe of ``kfs``, in that
+        order: one :meth:`connections_counts` for all of them, then
+        :meth:`apply_connections` one by one. Equal to the serial calls because
+        no apply writes what a count reads."""
+        kfs = [int(k) for k in kfs]
+        weights, ordered = self.connections_counts(kfs, ctx, counter)
+        for i, kf in enumerate(kfs):
+            self.apply_connections(kf, weights[i], *ordered[i])
 
     def get_connected_keyframes(self, kf: int) -> set:
         """KeyFrame::GetConnectedKeyFrames: every key of the weight map."""

@@ -725,6 +725,43 @@ int gf_keyframe_culling_counts_dev(gf_ctx* ctx, int nkf, int nkp, const int32_t*
                                    const int32_t* d_obs_gkp, int nobs, int ncand, const int32_t* d_cand,
                                    int32_t* d_counts, uint8_t* d_flags, void* stream);
 
+/* The counting and ordering of KeyFrame::UpdateConnections (src/KeyFrame.cc:
+ * 332-403) for nq query keyframes query[i] in one launch, over the flat tables
+ * of gf_keyframe_culling_counts (kf_off, slots, mp_bad, obs_off / obs_gkp; the
+ * octaves are not read). Every output has nq rows of nkf entries.
+ *   weights[i][k] = KFcounter[k] (:341-361): for every slot of the query in
+ *     slot order whose point p has 0 <= p < nmp and !mp_bad[p], every entry of
+ *     p's row whose keyframe is not the query adds one to that keyframe. A point
+ *     in two slots counts twice, a point whose row does not list the query
+ *     counts every observer, entries equal to -1 or outside [0, nkp) are
+ *     skipped, and no observer is tested for isBad(), as in the reference.
+ *     0 = not in the counter.
+ *   n_ordered[i], ordered_kf[i][0 .. n), ordered_w[i][0 .. n) =
+ *     mvpOrderedConnectedKeyFrames / mvOrderedWeights (:369-403): the keyframes
+ *     with weights >= 15 by (weight, index) descending, the higher index first
+ *     among equal weights (the sort of (int, KeyFrame*) pairs, reversed); when
+ *     none reaches 15 the single heaviest, the lowest index among equals (the
+ *     strict > of :378); n = 0 exactly when the counter is empty (the return
+ *     of :365). The rows are filled up with -1 / 0 past n.
+ * A query outside [0, nkf) gets a zero row and n = 0; a query may repeat. The
+ * graph updates of :376-418 are the caller's. Host arrays, synchronous;
+ * GF_ERR_ARG for kf_off / obs_off that do not start at 0 or decrease,
+ * GF_ERR_CAP above 4096 keypoints in a keyframe; nkf is bounded by memory
+ * only. */
+int gf_update_connections(gf_ctx* ctx, int nkf, const int32_t* kf_off, const int32_t* slots, int nmp,
+                          const uint8_t* mp_bad, const int32_t* obs_off, const int32_t* obs_gkp, int nq,
+                          const int32_t* query, int32_t* weights, int32_t* n_ordered, int32_t* ordered_kf,
+                          int32_t* ordered_w);
+/* Device family (src/KeyFrame.cc:332-403): device pointers, the totals nkp and
+ * nobs given by the caller, enqueued on stream without synchronising; every
+ * entry of the four outputs is written, so they need no clearing. The tables
+ * are not read on the host: a row outside [0, nobs) is clamped, a keyframe is
+ * walked up to 4096 slots. */
+int gf_update_connections_dev(gf_ctx* ctx, int nkf, int nkp, const int32_t* d_kf_off, const int32_t* d_slots, int nmp,
+                              const uint8_t* d_mp_bad, const int32_t* d_obs_off, const int32_t* d_obs_gkp, int nobs,
+                              int nq, const int32_t* d_query, int32_t* d_weights, int32_t* d_n_ordered,
+                              int32_t* d_ordered_kf, int32_t* d_ordered_w, void* stream);
+
 /* The graph assembly of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:
  * 1517-1675) over flat tables of the whole map: the five tables of
  * gf_keyframe_culling_counts (kf_off, octave, slots, mp_bad, obs_off /
