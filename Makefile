@@ -129,6 +129,13 @@ all: $(COVISREF)
 $(COVISREF): tests/helpers/covis_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of the resident map tables' journal apply and
+# regrow (tests/test_maptables_cpu.py, tests/test_maptables_gpu.py), same flags
+MAPTABLESREF = tests/helpers/libmaptablesref.so
+all: $(MAPTABLESREF)
+$(MAPTABLESREF): tests/helpers/maptables_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

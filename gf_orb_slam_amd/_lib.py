@@ -153,6 +153,10 @@ _PROTOS = {
     "gf_keyframe_culling_counts_dev": [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "gf_update_connections": [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "gf_update_connections_dev": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gf_map_tables_apply": [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P],
+    "gf_map_tables_apply_dev": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P],
+    "gf_map_tables_move": [_P, _I, _P, _P, _P, _P, _P],
+    "gf_map_tables_move_dev": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P],
     "gf_lba_graph": [_P, _P, _I, _P, _P],
     "gf_lba_graph_dev": [_P, _P, _I, _P, _P, _P],
     "gf_search_for_triangulation": [_P, _I, _P, _P, _P, _P, _I, _P, _P],

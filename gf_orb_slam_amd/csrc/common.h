@@ -50,7 +50,7 @@ struct gf_ctx {
     std::vector<hipEvent_t> event_pool;
     std::vector<hipEvent_t> prof_spent;  // stop events of multi-launch scopes that are not read
     // grow-only device scratch for the host-family wrappers (one slot per use)
-    static const int kSlots = 73;
+    static const int kSlots = 75;
     void* ws[kSlots] = {};
     size_t ws_size[kSlots] = {};
     // captured graphs (gf_frontend_capture) alive on this context: their

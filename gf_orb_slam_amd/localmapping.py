@@ -28,6 +28,12 @@ vectors, associates its points on the host and runs KeyFrame::UpdateConnections
 (``gf_update_connections_dev``: any number of keyframes in one launch) and the
 graph updates on the host (``LoopMap.apply_connections``). :class:`LocalMapper`
 strings the stages together as the body of ``LocalMapping::Run`` does.
+
+The three stages that count or assemble over the flat tables
+(:func:`culling_tables`, :func:`lba_tables`) rebuild and upload them per call,
+unless the map keeps them resident (``LoopMap.attach_tables``,
+``maptables.ResidentTables``): then they flush the map's journal and take the
+device tables from there.
 """
 from __future__ import annotations
 
@@ -217,27 +223,60 @@ def keyframe_culling_counts(kf_off, octave, slots, mp_bad, obs_off, obs_gkp, can
     return counts[:len(cand)]
 
 
+def _resident(tables, host: bool):
+    """The resident tables of a map for a stage: flushed, then their sizes and
+    either the host arrays (for an injected counter / assembler) or the device
+    tensors. Tables kept on the host by an applier serve host callables only: a
+    missing kernel path is an error, not a fallback."""
+    tables.flush()
+    if host:
+        return tables.sizes(), tables.host_arrays()
+    if tables.host:
+        raise GFError(-4, "tables resident on the host (applier=) need the stage's host counter / assembler")
+    return tables.sizes(), tables.arrays()
+
+
 class _CullTables:
     """The five tables of :func:`culling_tables` for one KeyFrameCulling,
     resident on the device (uploaded once) unless a host ``counter`` is
     injected. After a cull only what the surgery touched is written again:
     -1 over the erased observations (the CSR is never rebuilt), the bad flags
     of the points that turned bad and -1 in the slots their SetBadFlag
-    cleared."""
+    cleared. With resident tables attached to the map (``map.tables``) nothing
+    is built or uploaded: the tables are flushed and taken from there, and a
+    refresh is another flush, ``set_bad_keyframe`` having journalled its
+    surgery."""
+
+    NAMES = ("kf_off", "octave", "slots", "mp_bad", "obs_off", "obs_gkp")
 
     def __init__(self, map, ctx, counter=None):
         self.map, self.ctx, self.counter = map, ctx, counter
-        (self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off, self.obs_gkp,
-         self.where) = culling_tables(map)
         self.launches = 0
+        self.res = getattr(map, "tables", None)
         if counter is None:
             import torch
 
             self.torch = torch
             self.dev = torch.device("cuda", torch.cuda.current_device())
+        if self.res is not None:
+            self._take()
+            return
+        (self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off, self.obs_gkp,
+         self.where) = culling_tables(map)
+        self.n = dict(nkf=len(self.kf_off) - 1, nkp=len(self.slots), nmp=len(self.mp_bad), nobs=len(self.obs_gkp))
+        if counter is None:
             self.d = [self._t(a) for a in (self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off,
                                            self.obs_gkp)]
-            torch.cuda.current_stream().synchronize()
+            self.torch.cuda.current_stream().synchronize()
+
+    def _take(self):
+        """The resident tables after a flush (which may have reallocated them)."""
+        self.n, arrays = _resident(self.res, self.counter is not None)
+        if self.counter is not None:
+            self.kf_off, self.octave, self.slots, self.mp_bad, self.obs_off, self.obs_gkp = (
+                arrays[name] for name in self.NAMES)
+        else:
+            self.d = [arrays[name] for name in self.NAMES]
 
     def _t(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
@@ -253,16 +292,18 @@ class _CullTables:
         d_cand = self._t(cand)
         d_counts = torch.empty(len(cand) * 2, dtype=torch.int32, device=self.dev)
         torch.cuda.current_stream().synchronize()  # the uploads and refreshes ran on torch's stream
-        d = self.d
-        check(lib().gf_keyframe_culling_counts_dev(self.ctx.handle, len(self.kf_off) - 1, len(self.slots), ptr(d[0]),
-                                                   ptr(d[1]), ptr(d[2]), len(self.mp_bad), ptr(d[3]), ptr(d[4]),
-                                                   ptr(d[5]), len(self.obs_gkp), len(cand), ptr(d_cand),
-                                                   ptr(d_counts), None, self.ctx.stream))
+        d, n = self.d, self.n
+        check(lib().gf_keyframe_culling_counts_dev(self.ctx.handle, n["nkf"], n["nkp"], ptr(d[0]), ptr(d[1]),
+                                                   ptr(d[2]), n["nmp"], ptr(d[3]), ptr(d[4]), ptr(d[5]), n["nobs"],
+                                                   len(cand), ptr(d_cand), ptr(d_counts), None, self.ctx.stream))
         self.ctx.sync()
         return d_counts.cpu().numpy().reshape(-1, 2)
 
     def refresh(self, log):
         """Point updates after ``set_bad_keyframe`` returned ``log``."""
+        if self.res is not None:
+            self._take()
+            return
         gone = np.asarray([self.where[(p, k)] for p, k, _ in log["observations"]], np.int64)
         bad = np.asarray(log["points_bad"], np.int64)
         cleared = np.asarray([self.kf_off[k] + i for k, i in log["cleared"]], np.int64)
@@ -376,19 +417,31 @@ class _CovisTables:
     """The tables of :func:`culling_tables` that UpdateConnections reads
     (``kf_off``, ``slots``, ``mp_bad``, ``obs_off``, ``obs_gkp``) for one
     ``LoopMap.connections_counts``, uploaded once unless a host ``counter`` is
-    injected."""
+    injected. With resident tables attached to the map (``map.tables``) they
+    are flushed and taken from there instead."""
+
+    NAMES = ("kf_off", "slots", "mp_bad", "obs_off", "obs_gkp")
 
     def __init__(self, map, ctx=None, counter=None):
         self.counter = counter
-        self.kf_off, _, self.slots, self.mp_bad, self.obs_off, self.obs_gkp, _ = culling_tables(map)
         self.nkf = map.nkf
         if counter is None:
             import torch
 
             self.ctx, self.torch = ctx or default_context(), torch
             self.dev = torch.device("cuda", torch.cuda.current_device())
+        if getattr(map, "tables", None) is not None:
+            self.n, arrays = _resident(map.tables, counter is not None)
+            if counter is not None:
+                self.kf_off, self.slots, self.mp_bad, self.obs_off, self.obs_gkp = (arrays[n] for n in self.NAMES)
+            else:
+                self.d = [arrays[n] for n in self.NAMES]
+            return
+        self.kf_off, _, self.slots, self.mp_bad, self.obs_off, self.obs_gkp, _ = culling_tables(map)
+        self.n = dict(nkf=len(self.kf_off) - 1, nkp=len(self.slots), nmp=len(self.mp_bad), nobs=len(self.obs_gkp))
+        if counter is None:
             self.d = [self._t(a) for a in (self.kf_off, self.slots, self.mp_bad, self.obs_off, self.obs_gkp)]
-            torch.cuda.current_stream().synchronize()
+            self.torch.cuda.current_stream().synchronize()
 
     def _t(self, a):
         return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
@@ -407,9 +460,9 @@ class _CovisTables:
             d_query = self._t(query)
             d_out = torch.empty((3 * nkf + 1) * nq, dtype=torch.int32, device=self.dev)  # weights | kf | w | n
             torch.cuda.current_stream().synchronize()  # the uploads ran on torch's stream
-            d, row = self.d, nq * nkf
-            check(lib().gf_update_connections_dev(self.ctx.handle, nkf, len(self.slots), ptr(d[0]), ptr(d[1]),
-                                                  len(self.mp_bad), ptr(d[2]), ptr(d[3]), ptr(d[4]), len(self.obs_gkp),
+            d, row, n = self.d, nq * nkf, self.n
+            check(lib().gf_update_connections_dev(self.ctx.handle, nkf, n["nkp"], ptr(d[0]), ptr(d[1]),
+                                                  n["nmp"], ptr(d[2]), ptr(d[3]), ptr(d[4]), n["nobs"],
                                                   nq, ptr(d_query), ptr(d_out), ptr(d_out[3 * row:]),
                                                   ptr(d_out[row:]), ptr(d_out[2 * row:]), self.ctx.stream))
             self.ctx.sync()
@@ -521,14 +574,18 @@ class LocalMapper:
     counter / assembler / solver: host callables handed to the stages that
     take them (``process_new_keyframe``, ``keyframe_culling``;
     ``local_bundle_adjustment``); stages: a dict replacing stage functions by
-    name (the CPU tests record the order with it)."""
+    name (the CPU tests record the order with it). resident: attach resident
+    flat tables to the map at construction (``LoopMap.attach_tables``;
+    ``applier`` as there, for the host callables), unless it has some."""
 
     STAGES = ("process_new_keyframe", "map_point_culling", "create_new_map_points", "search_in_neighbors",
               "local_bundle_adjustment", "keyframe_culling")
 
     def __init__(self, map, voc, ctx=None, db=None, detector=None, levelsup=4, counter=None, cull_counter=None,
-                 assembler=None, solver=None, stages=None):
+                 assembler=None, solver=None, stages=None, resident=False, applier=None):
         self.map, self.voc, self.ctx, self.db, self.detector = map, voc, ctx, db, detector
+        if resident and map.tables is None:
+            map.attach_tables(ctx=ctx, applier=applier)
         self.levelsup, self.recent = levelsup, []
         self.counter, self.cull_counter, self.assembler, self.solver = counter, cull_counter, assembler, solver
         self.stages = dict(process_new_keyframe=process_new_keyframe, map_point_culling=map_point_culling,
@@ -838,18 +895,32 @@ def lba_tables(map) -> dict:
     undistorted keypoint positions and poses, the points' positions,
     ``inv_sigma2`` per level, the camera and ``kf0``, the index of the keyframe
     with mnId 0 (-1 without one)."""
-    from .optimizer import inv_level_sigma2
-
     kf_off, octave, slots, mp_bad, obs_off, obs_gkp, where = culling_tables(map)
     xy = [np.zeros((0, 2), np.float32)] + [np.stack([k["x"], k["y"]], axis=1).astype(np.float32) for k in map.kf_kps]
+    return dict(kf_off=kf_off, octave=octave, slots=slots, mp_bad=mp_bad, obs_off=obs_off, obs_gkp=obs_gkp, where=where,
+                kp_xy=np.ascontiguousarray(np.concatenate(xy)), **_lba_dense(map))
+
+
+def _lba_dense(map) -> dict:
+    """The small dense arrays of :func:`lba_tables` that code writes directly
+    (``kf_bad``, ``kf_Tcw``, ``mp_pos``), ``inv_sigma2``, the camera and
+    ``kf0``: vectorised and small, so taken whole whenever a stage asks."""
+    from .optimizer import inv_level_sigma2
+
     first = np.nonzero(np.asarray(map.kf_id) == 0)[0]
     i = map.info
-    return dict(kf_off=kf_off, octave=octave, slots=slots, mp_bad=mp_bad, obs_off=obs_off, obs_gkp=obs_gkp, where=where,
-                kf_bad=map.kf_bad.astype(np.uint8), kp_xy=np.ascontiguousarray(np.concatenate(xy)),
-                kf_Tcw=np.ascontiguousarray(map.Tcw, np.float32).reshape(-1, 16),
+    return dict(kf_bad=map.kf_bad.astype(np.uint8), kf_Tcw=np.ascontiguousarray(map.Tcw, np.float32).reshape(-1, 16),
                 mp_pos=np.ascontiguousarray(map.mps["pos"], np.float32).reshape(-1, 3),
                 inv_sigma2=inv_level_sigma2(i.nlevels, i.scale_factor), cam=np.asarray([i.fx, i.fy, i.cx, i.cy], np.float32),
                 kf0=int(first[0]) if len(first) else -1)
+
+
+def lba_tables_resident(map) -> dict:
+    """:func:`lba_tables` from the map's resident tables on the host (for an
+    injected assembler): the rows carry their -1 padding, ``where`` is None."""
+    n, a = _resident(map.tables, True)
+    return dict({name: a[name] for name in ("kf_off", "octave", "slots", "mp_bad", "obs_off", "obs_gkp")}, where=None,
+                kp_xy=a["kp_xy"].reshape(-1, 2), **_lba_dense(map))
 
 
 def lba_local_keyframes(map, cur: int) -> list:
@@ -867,8 +938,8 @@ def _lba_struct(t: dict, arrays: dict) -> LBATables:
         raise GFError(-1, "table lengths disagree")
     for name, _, per, size in _LBA_TABLES:
         want = (n[size[:-1]] + 1 if size.endswith("+") else n[size]) * per
-        if np.asarray(t[name]).size != want:
-            raise GFError(-1, f"table lengths disagree: {name} has {np.asarray(t[name]).size} elements, not {want}")
+        if _n_el(t[name]) != want:
+            raise GFError(-1, f"table lengths disagree: {name} has {_n_el(t[name])} elements, not {want}")
     q = LBATables(n["nkf"], n["nkp"], n["nmp"], n["nobs"], n["nlevels"], int(t["kf0"]),
                   *[ptr(arrays[name]) if _n_el(arrays[name]) else None for name, *_ in _LBA_TABLES])
     q.cam[:] = [float(x) for x in np.asarray(t["cam"], np.float32).reshape(4)]
@@ -911,15 +982,26 @@ def lba_graph_arrays(tables: dict, local, ctx=None) -> dict:
 class _LBATables:
     """The tables of :func:`lba_tables` for one LocalBundleAdjustment, resident
     on the device (uploaded once) with the bound-sized output buffers of
-    ``gf_lba_graph_dev`` next to them."""
+    ``gf_lba_graph_dev`` next to them. With resident tables attached to the
+    map (``map.tables``) the big tables are flushed and taken from there and
+    only the small dense arrays of :func:`_lba_dense` are uploaded; ``nobs`` is
+    then the used length of ``obs_gkp``, padding included, and the bound-sized
+    outputs follow it."""
 
     def __init__(self, map, ctx):
         import torch
 
         self.ctx, self.torch = ctx, torch
-        self.t = lba_tables(map)
         self.dev = torch.device("cuda", torch.cuda.current_device())
-        self.d = {name: self._t(np.ascontiguousarray(self.t[name], dt).reshape(-1)) for name, dt, _, _ in _LBA_TABLES}
+        if getattr(map, "tables", None) is not None:
+            _, arrays = _resident(map.tables, False)
+            self.t = dict(arrays, **_lba_dense(map))
+            self.d = {name: arrays[name] if name in arrays else
+                      self._t(np.ascontiguousarray(self.t[name], dt).reshape(-1)) for name, dt, _, _ in _LBA_TABLES}
+        else:
+            self.t = lba_tables(map)
+            self.d = {name: self._t(np.ascontiguousarray(self.t[name], dt).reshape(-1))
+                      for name, dt, _, _ in _LBA_TABLES}
         self.q = _lba_struct(self.t, self.d)
         bound = (max(self.q.nkf, 1), max(self.q.nmp, 1), max(self.q.nobs, 1))
         tdt = {np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}
@@ -1013,7 +1095,7 @@ def local_bundle_adjustment(map, cur: int, stop_flag=None, ctx=None, assembler=N
         g = tables.download()
         lap("download")
     else:
-        tables = lba_tables(map)
+        tables = lba_tables(map) if getattr(map, "tables", None) is None else lba_tables_resident(map)
         lap("tables")
         g = assembler(tables, local)
         lap("assembly")

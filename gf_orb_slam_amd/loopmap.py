@@ -83,6 +83,19 @@ class LoopMap:
         # mBowVec as (words, values) / mFeatVec as a FeatureVector, None until ComputeBoW ran
         self.kf_bow = [None] * self.nkf
         self.kf_fv = [None] * self.nkf
+        # the resident flat tables (maptables.ResidentTables), None = not attached: every method below that
+        # writes obs, slots or mp_bad logs what it wrote there
+        self.tables = None
+
+    def attach_tables(self, ctx=None, applier=None, **policy):
+        """Keep the flat tables of ``localmapping.culling_tables`` resident and
+        up to date by journal (``maptables.ResidentTables``; ``applier`` and
+        the capacity ``policy`` as there): the stages that read them then flush
+        the journal instead of rebuilding them. -> the tables."""
+        from .maptables import ResidentTables
+
+        self.tables = ResidentTables(self, ctx, applier, **policy)
+        return self.tables
 
     # ------------------------------------------------------------ Map
     def add_keyframe(self, kps, desc, slots, Tcw, kf_id=None) -> int:
@@ -124,6 +137,7 @@ class LoopMap:
         self.kf_bow.append(None)
         self.kf_fv.append(None)
         self.nkf = k + 1
+        if self.tables is not None: self.tables.log_add_keyframe(k)
         return k
 
     # ------------------------------------------------------------ MapPoint
@@ -134,6 +148,7 @@ class LoopMap:
     def add_observation(self, p: int, kf: int, idx: int) -> None:
         """MapPoint::AddObservation (MapPoint.cc:77-81): overwrites."""
         self.obs[p][int(kf)] = int(idx)
+        if self.tables is not None: self.tables.log_obs_set(p, kf, idx)
 
     def new_map_point(self, pos, ref_kf: int) -> int:
         """``new MapPoint(pos, pRefKF, pMap)`` + ``Map::AddMapPoint``
@@ -155,6 +170,7 @@ class LoopMap:
         self.corrected_by = np.append(self.corrected_by, np.int32(-1))
         self.corrected_ref = np.append(self.corrected_ref, np.int32(-1))
         self.fuse_candidate_for = np.append(self.fuse_candidate_for, np.int64(-1))
+        if self.tables is not None: self.tables.log_new_map_point(p)
         return p
 
     def set_bad_point(self, p: int) -> None:
@@ -166,6 +182,7 @@ class LoopMap:
         self.mp_bad[p] = True
         for kf in sorted(obs):
             self.slots[kf][obs[kf]] = -1
+        if self.tables is not None: self.tables.log_set_bad(p, obs)
 
     def erase_observation(self, p: int, kf: int) -> bool:
         """MapPoint::EraseObservation (MapPoint.cc:83-103): nothing when ``kf``
@@ -178,6 +195,7 @@ class LoopMap:
         if kf not in self.obs[p]:
             return False
         del self.obs[p][kf]
+        if self.tables is not None: self.tables.log_obs_erase(p, kf)
         if self.ref_kf[p] == kf and self.obs[p]:
             self.ref_kf[p] = min(self.obs[p])
         if len(self.obs[p]) <= 2:
@@ -205,6 +223,7 @@ class LoopMap:
                 self.add_observation(b, kf, idx)
             else:
                 self.slots[kf][idx] = -1  # EraseMapPointMatch
+        if self.tables is not None: self.tables.log_replace(a, obs)
         self.compute_distinctive_descriptors([b])
 
     def compute_distinctive_descriptors(self, ids) -> None:
@@ -337,6 +356,7 @@ class LoopMap:
     def erase_map_point_match(self, kf: int, idx: int) -> None:
         """KeyFrame::EraseMapPointMatch(idx)."""
         self.slots[int(kf)][int(idx)] = -1
+        if self.tables is not None: self.tables.log_slot(kf, idx, -1)
 
     def erase_connection(self, kf: int, other: int) -> None:
         """KeyFrame::EraseConnection (KeyFrame.cc:596-610)."""
@@ -433,6 +453,7 @@ class LoopMap:
     def add_map_point(self, kf: int, p: int, idx: int) -> None:
         """KeyFrame::AddMapPoint."""
         self.slots[kf][idx] = p
+        if self.tables is not None: self.tables.log_slot(kf, idx, p)
 
     def get_map_points(self, kf: int) -> set:
         """KeyFrame::GetMapPoints (KeyFrame.cc:238-251): the non-bad points of

@@ -762,6 +762,80 @@ int gf_update_connections_dev(gf_ctx* ctx, int nkf, int nkp, const int32_t* d_kf
                               int nq, const int32_t* d_query, int32_t* d_weights, int32_t* d_n_ordered,
                               int32_t* d_ordered_kf, int32_t* d_ordered_w, void* stream);
 
+/* Resident map tables: the flat tables of gf_keyframe_culling_counts kept on
+ * the device and updated in place by a journal of the map's own writes. The
+ * observation table is a slack CSR: obs_off[p] .. obs_off[p + 1] is the
+ * capacity of row p; inside it sit the live entries in ascending order of the
+ * global keypoint index kf_off[kf] + idx (= observation-map order), then -1 up
+ * to the capacity. The three consumers above skip -1, so they read such a
+ * table as it is.
+ *
+ * gf_map_tables_apply applies one journal:
+ *   slot_g[nslot], slot_v[nslot]: slots[slot_g[i]] = slot_v[i], what
+ *     KeyFrame::AddMapPoint, ReplaceMapPointMatch (a point id) and
+ *     EraseMapPointMatch (-1) write (src/KeyFrame.cc:210-236);
+ *   bad_p[nbad]: mp_bad[bad_p[i]] = 1 (mbBad of MapPoint::SetBadFlag,
+ *     src/MapPoint.cc:117-131, and Replace, :136-170);
+ *   the observation ops, stable-sorted by point: row_ids[nrows] the touched
+ *     points, each once; row_op_off[nrows + 1] the ranges into ops[nops][3] =
+ *     (kind, kf, idx), applied to the row serially in journal order:
+ *       GF_MT_OBS_SET   mObservations[kf] = idx (MapPoint::AddObservation,
+ *         MapPoint.cc:77-81): an entry inside [kf_off[kf], kf_off[kf + 1]) is
+ *         overwritten with kf_off[kf] + idx, otherwise the entry is inserted
+ *         at its ascending place (after the entries below kf_off[kf]);
+ *       GF_MT_OBS_ERASE mObservations.erase(kf) (EraseObservation, :83-103):
+ *         the entry inside the keyframe's range goes, nothing when absent;
+ *       GF_MT_OBS_CLEAR mObservations.clear() (SetBadFlag, Replace).
+ *     The row is then written back as its live entries followed by -1 up to
+ *     the capacity; every entry of a touched row is written.
+ * Targets must be unique (the caller keeps the last write per slot).
+ * status[0] counts the rows left byte for byte untouched because their final
+ * length exceeds their capacity or a length on the way exceeds GF_MT_ROW
+ * entries (the length on the way may exceed the capacity); status[1] counts the
+ * ops skipped because their p, g, kf, idx or kind is out of range (a row id
+ * outside [0, nmp) skips all its ops). An entry >= 0 is live. Host arrays,
+ * synchronous, slots / mp_bad / obs_gkp updated in place; GF_ERR_ARG for
+ * kf_off / obs_off / row_op_off that do not start at 0, decrease or disagree
+ * with the lengths, row_ids that do not strictly increase and repeated slot
+ * targets. */
+enum { GF_MT_OBS_SET = 0, GF_MT_OBS_ERASE = 1, GF_MT_OBS_CLEAR = 2 };
+#define GF_MT_ROW 1024
+int gf_map_tables_apply(gf_ctx* ctx, int nkf, const int32_t* kf_off, int32_t* slots, int nmp, uint8_t* mp_bad,
+                        const int32_t* obs_off, int32_t* obs_gkp, int nslot, const int32_t* slot_g,
+                        const int32_t* slot_v, int nbad, const int32_t* bad_p, int nrows, const int32_t* row_ids,
+                        const int32_t* row_op_off, int nops, const int32_t* ops, int32_t* status);
+/* Device family (MapPoint.cc:77-81, :83-103, :117-131, :136-170; KeyFrame::
+ * AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch): device pointers,
+ * the totals nkp and nobs given by the caller, enqueued on stream without
+ * synchronising. d_status[2] is cleared on the stream first. Nothing is read on
+ * the host: a row outside [0, nobs) is clamped, an op range outside [0, nops)
+ * too; repeated targets or row ids race (each write stays inside the tables). */
+int gf_map_tables_apply_dev(gf_ctx* ctx, int nkf, int nkp, const int32_t* d_kf_off, int32_t* d_slots, int nmp,
+                            uint8_t* d_mp_bad, const int32_t* d_obs_off, int32_t* d_obs_gkp, int nobs, int nslot,
+                            const int32_t* d_slot_g, const int32_t* d_slot_v, int nbad, const int32_t* d_bad_p,
+                            int nrows, const int32_t* d_row_ids, const int32_t* d_row_op_off, int nops,
+                            const int32_t* d_ops, int32_t* d_status, void* stream);
+
+/* The regrow of a slack CSR: every row's live entries (>= 0), compacted and in
+ * order, are copied from old_gkp[old_off[p] .. old_off[p + 1]) to
+ * new_gkp[new_off[p] ..] and the rest of the new capacity is filled with -1, so
+ * every entry of the new table is written. Entries equal to -1 anywhere in an
+ * old row are legal (the point updates of a cull leave them). A row whose new
+ * capacity is below its live count is written as all -1 and counted in
+ * status[0]. The observation maps themselves do not change: this stands for no
+ * line of the reference, it makes room for the MapPoint::AddObservation
+ * (MapPoint.cc:77-81) entries of the journal that follows. Host arrays,
+ * synchronous; the two tables must not overlap; GF_ERR_ARG for offsets that do
+ * not start at 0 or decrease. */
+int gf_map_tables_move(gf_ctx* ctx, int nmp, const int32_t* old_off, const int32_t* old_gkp, const int32_t* new_off,
+                       int32_t* new_gkp, int32_t* status);
+/* Device family: device pointers, the totals nobs_old and nobs_new given by the
+ * caller, enqueued on stream without synchronising; d_status[1] is cleared on
+ * the stream first. Rows are clamped to the tables they lie in. */
+int gf_map_tables_move_dev(gf_ctx* ctx, int nmp, const int32_t* d_old_off, const int32_t* d_old_gkp, int nobs_old,
+                           const int32_t* d_new_off, int32_t* d_new_gkp, int nobs_new, int32_t* d_status,
+                           void* stream);
+
 /* The graph assembly of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:
  * 1517-1675) over flat tables of the whole map: the five tables of
  * gf_keyframe_culling_counts (kf_off, octave, slots, mp_bad, obs_off /
