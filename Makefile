@@ -136,6 +136,14 @@ all: $(MAPTABLESREF)
 $(MAPTABLESREF): tests/helpers/maptables_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of Tracking::CreateInitialMap around the solver:
+# the map's points and graph, and the median-depth scaling
+# (tests/test_initmap_cpu.py, tests/test_initmap_gpu.py), same flags
+INITMAPREF = tests/helpers/libinitmapref.so
+all: $(INITMAPREF)
+$(INITMAPREF): tests/helpers/initmap_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)
@@ -146,6 +154,12 @@ $(DROPIN): tests/cpp/dropin_frontend.cpp include/gfslam/orbslam.h include/gfslam
 SEQDRV = tests/cpp/sequence_driver
 all: $(SEQDRV)
 $(SEQDRV): tests/cpp/sequence_driver.cpp include/gfslam/orbslam.h include/gfslam/abi.h $(LIB)
+	$(CXX) -O2 -std=c++17 -Iinclude $< -Lgf_orb_slam_amd -lgfslam -Wl,-rpath,'$$ORIGIN/../../gf_orb_slam_amd' -o $@
+
+# drop-in Optimizer::BundleAdjustment caller (tests/test_initmap_dropin_gpu.py)
+BADRV = tests/cpp/ba_driver
+all: $(BADRV)
+$(BADRV): tests/cpp/ba_driver.cpp include/gfslam/orbslam.h include/gfslam/abi.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Iinclude $< -Lgf_orb_slam_amd -lgfslam -Wl,-rpath,'$$ORIGIN/../../gf_orb_slam_amd' -o $@
 
 # diagnostic build: k_active_match phase stamps (scripts/am_stamps.py), never the product

@@ -209,6 +209,11 @@ _PROTOS = {
     "gf_ba_plan_destroy": [_P],
     "gf_ba_plan_solve_stop": [_P, _P, _P, _P],
     "gf_local_ba_stop": [_P, _P, _P, _P],
+    "gf_ba_plan_create_iters": [_P, _I, _P, _I, _P],
+    "gf_bundle_adjustment": [_P, _P, _I, _P, _P],
+    "gf_ba_plan_results_dev": [_P, _I, _P, _P, _P],
+    "gf_initial_map_points_dev": [_P, _P, _I, _P, _P, _P],
+    "gf_initial_map_finish_dev": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "gf_orb_extract_ptrs_dev": [_P, _I, _P, _I, _P, _P, _P, _I, _P],
     "gf_frustum_list_dev": [_P, _P, _I, _P, _P, _I, _P, _P, _F, _P, _P, _P],
     "gf_match_project_list_dev": [_P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _F, _F, _P, _P, _P, _P],

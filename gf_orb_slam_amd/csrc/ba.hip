@@ -30,6 +30,11 @@
 //                   at the end of optimize(5) / optimize(10) the outlier pass
 //                   (Optimizer.cc:1680-1698, 1724-1743)
 //
+// The schedule (the iteration caps of the two optimize() calls and whether the
+// outlier passes run) is plan state, BAArena::cap / ::outlier. The local form
+// is {5, 10} with the passes; Optimizer::BundleAdjustment (Optimizer.cc:36-142)
+// is {nIterations, -} without them: one optimize() call, no edge leaves.
+//
 // Every kernel reads the problem's state first and returns at once when the
 // step does not concern it, so the host enqueues steps blindly and polls the
 // done flags every few steps. Floating-point parity with the oracle is a
@@ -53,7 +58,8 @@ constexpr int BA_MAXSPLIT = 64;  // split-K of the Schur GEMM (per plan: more sp
 constexpr int BA_MAXFREE = 32;
 constexpr int BA_MAXN = 6 * BA_MAXFREE;  // LDS of k_ba_solve
 constexpr int BA_MAXPTS = 65536;
-constexpr int BA_MAXSTEPS = 400;
+constexpr int BA_MAXSTEPS = 400;  // step guard of the 5 + 10 schedule
+constexpr int BA_MAXITERS = 64;   // cap of gf_bundle_adjustment's nIterations
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -68,7 +74,7 @@ struct BADesc {
 };
 
 struct BAState {
-    int round;     // 0: optimize(5), 1: optimize(10), 2: done
+    int round;     // 0: first optimize() call, 1: second, 2: done
     int iter, q;   // outer iteration of the round, trial of the iteration
     int need_lin;  // next step starts an iteration (errors + buildSystem)
     int cur;       // estimate buffer holding the current state
@@ -126,6 +132,11 @@ struct BAArena {
     // call at its next iteration boundary (SparseOptimizer::optimize checks
     // terminate() before each iteration, sparse_optimizer.cpp:376)
     const int* stop;
+    // schedule: iteration caps of the two optimize() calls; outlier != 0: the
+    // outlier pass follows each call (LocalBundleAdjustment), == 0: the first
+    // call runs alone and no edge is checked or removed (BundleAdjustment)
+    int cap[2];
+    int outlier;
 };
 
 __device__ __forceinline__ gfse3::SE3 load_T(const BAArena& A, int buf, int gk) {
@@ -314,7 +325,8 @@ __global__ __launch_bounds__(256) void k_ba_init(BAArena A) {
         BAState s{};
         s.round = d.nedges > 0 ? 0 : 2;
         s.iters[0] = d.nedges > 0 ? 0 : -1;
-        s.iters[1] = d.nedges > 0 ? 0 : -1;
+        s.iters[1] = d.nedges > 0 && A.outlier ? 0 : -1;
+        if (!A.outlier && A.cap[0] == 0) s.round = 2;  // optimize(0): initialised, no iteration
         s.need_lin = 1;
         s.ni = 2;
         A.st[p] = s;
@@ -1291,7 +1303,7 @@ __global__ __launch_bounds__(1024) void k_ba_decide(BAArena A) {
                 term = st.nbad >= 3;
             }
             st.iter++;
-            if (term || st.iter >= (st.round == 0 ? 5 : 10)) {
+            if (term || st.iter >= (st.round == 0 ? A.cap[0] : A.cap[1])) {
                 end = 1;
             } else {
                 st.need_lin = 1;
@@ -1304,6 +1316,10 @@ __global__ __launch_bounds__(1024) void k_ba_decide(BAArena A) {
     }
     __syncthreads();
     if (!s_end) return;
+    if (!A.outlier) {  // BundleAdjustment: optimize(nIterations) was the whole run
+        if (tid == 0) A.st[p].round = 2;
+        return;
+    }
     const BAState st = A.st[p];
     const int round = st.round, cur = st.cur;
     double* Ht = A.panel + d.panel0;
@@ -1413,6 +1429,11 @@ struct gf_ba_plan {
     BAState* h_state = nullptr;  // pinned
     BADesc* d_desc = nullptr;
     int* d_stop = nullptr;       // device copy of the caller's stop flag
+    // blind steps after which the host loop gives up: an iteration takes at
+    // most 10 trials (one step each) and a raised stop flag ends a round in
+    // one step more
+    int max_steps = BA_MAXSTEPS;
+    int first_chunk = 12;
     std::vector<uint8_t> h_out;  // scratch for results
 };
 
@@ -1759,7 +1780,23 @@ int gf_ba_plan_create(gf_ctx* ctx, int nprob, const gf_ba_problem* probs, gf_ba_
     A.wg_scale = w3;
     A.out_T = oT;
     A.out_X = oX;
+    A.cap[0] = 5;
+    A.cap[1] = 10;
+    A.outlier = 1;
     *out = P;
+    return GF_OK;
+}
+
+int gf_ba_plan_create_iters(gf_ctx* ctx, int nprob, const gf_ba_problem* probs, int niterations, gf_ba_plan** out) {
+    GF_CHECK(niterations >= 0 && niterations <= BA_MAXITERS, GF_ERR_ARG, "niterations outside [0, 64]");
+    int rc = gf_ba_plan_create(ctx, nprob, probs, out);
+    if (rc) return rc;
+    gf_ba_plan* P = *out;
+    P->A.cap[0] = niterations;
+    P->A.cap[1] = 0;
+    P->A.outlier = 0;
+    P->max_steps = 10 * niterations + 1;
+    P->first_chunk = std::min(12, std::max(1, niterations));
     return GF_OK;
 }
 
@@ -1799,20 +1836,21 @@ int gf_ba_plan_solve_stop(gf_ba_plan* P, void* stream, const volatile uint8_t* s
     // Steps are enqueued blindly in chunks (a finished problem's kernels
     // return at once) and the state is read back after each chunk. The first
     // chunk covers the usual optimize(5) + optimize(10) run (15 iterations,
-    // one trial each), the later ones are short; every chunk ends with the
+    // one trial each; at most nIterations steps for BundleAdjustment), the
+    // later ones are short; every chunk ends with the
     // output conversion (idempotent), so the chunk that finishes the last
     // problem needs no further launch and wait. A host round trip costs about
     // as much as two no-op steps.
     int n = 0;
     bool done = false;
     while (!done) {
-        GF_CHECK(n < BA_MAXSTEPS, GF_ERR_HIP, "local BA did not terminate");
+        GF_CHECK(n < P->max_steps, GF_ERR_HIP, "BA did not terminate");
         if (stop_flag && *stop_flag && !stop_sent) {  // the caller raised mbAbortBA
             static const int one = 1;
             GF_HIP(hipMemcpyAsync(P->d_stop, &one, sizeof(int), hipMemcpyHostToDevice, s));
             stop_sent = true;
         }
-        const int chunk = n == 0 ? 12 : 4;
+        const int chunk = n == 0 ? P->first_chunk : 4;
         for (int c = 0; c < chunk; c++, n++) {
             int rc = ba_launch_step(P, s);
             if (rc) return rc;
@@ -1851,6 +1889,27 @@ int gf_ba_plan_results(gf_ba_plan* P, gf_ba_result* res) {
         res[p].iterations[1] = P->h_state[p].iters[1];
     }
     return GF_OK;
+}
+
+int gf_ba_plan_results_dev(gf_ba_plan* P, int p, const float** kf_Tcw, const float** pt_pos,
+                           const int32_t** iterations) {
+    GF_CHECK(P && p >= 0 && p < P->nprob, GF_ERR_ARG, "problem index out of range");
+    if (kf_Tcw) *kf_Tcw = P->A.out_T + (size_t)P->desc[p].kf0 * 16;
+    if (pt_pos) *pt_pos = P->A.out_X + (size_t)P->desc[p].pt0 * 3;
+    if (iterations) *iterations = P->A.st[p].iters;
+    return GF_OK;
+}
+
+int gf_bundle_adjustment(gf_ctx* ctx, const gf_ba_problem* prob, int niterations, gf_ba_result* res,
+                         const volatile uint8_t* stop_flag) {
+    GF_CHECK(ctx && prob && res, GF_ERR_ARG, "null arg");
+    gf_ba_plan* P = nullptr;
+    int rc = gf_ba_plan_create_iters(ctx, 1, prob, niterations, &P);
+    if (rc) return rc;
+    rc = gf_ba_plan_solve_stop(P, nullptr, stop_flag, nullptr);
+    if (!rc) rc = gf_ba_plan_results(P, res);
+    gf_ba_plan_destroy(P);
+    return rc;
 }
 
 int gf_local_ba(gf_ctx* ctx, const gf_ba_problem* prob, gf_ba_result* res) {

@@ -606,7 +606,9 @@ int Optimizer::PoseOptimization(Frame* pFrame) {
     return ninl;
 }
 
-void Optimizer::LocalBundleAdjustment(LocalBAWindow* w, bool* pbStopFlag) {
+// the window as a gf_ba_problem, solved by the local schedule (niterations < 0)
+// or by one optimize(niterations), and written back
+static void solve_window(Optimizer::LocalBAWindow* w, int niterations, bool* pbStopFlag) {
     if (!w) throw GpuError(GF_ERR_ARG, "null window");
     gf_ba_problem P{};
     P.nkf = (int32_t)w->kf_kind.size();
@@ -631,11 +633,20 @@ void Optimizer::LocalBundleAdjustment(LocalBAWindow* w, bool* pbStopFlag) {
     R.pt_pos = X.data();
     R.edge_outlier = w->edge_outlier.data();
     static_assert(sizeof(bool) == 1, "bool flag read as a byte");
-    check(gf_local_ba_stop(Context(), &P, &R, reinterpret_cast<const volatile uint8_t*>(pbStopFlag)));
+    const volatile uint8_t* stop = reinterpret_cast<const volatile uint8_t*>(pbStopFlag);
+    check(niterations < 0 ? gf_local_ba_stop(Context(), &P, &R, stop)
+                          : gf_bundle_adjustment(Context(), &P, niterations, &R, stop));
     w->kf_Tcw = T;
     w->pt_pos = X;
     w->iterations[0] = R.iterations[0];
     w->iterations[1] = R.iterations[1];
+}
+
+void Optimizer::LocalBundleAdjustment(LocalBAWindow* w, bool* pbStopFlag) { solve_window(w, -1, pbStopFlag); }
+
+void Optimizer::BundleAdjustment(LocalBAWindow* w, int nIterations, bool* pbStopFlag) {
+    if (nIterations < 0) throw GpuError(GF_ERR_ARG, "nIterations < 0");
+    solve_window(w, nIterations, pbStopFlag);
 }
 
 }  // namespace ORB_SLAM

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "match_common.h"
+#include "normaldepth.h"
 
 #define NS_THREADS 256
 #define NS_TH_LOW 50
@@ -115,10 +116,6 @@ __global__ __launch_bounds__(NS_THREADS) void k_fuse_search(FrameConst fc, const
     }
 }
 
-__device__ __forceinline__ float norm3(const float* d) {  // cv::norm: a double sum, cast to float
-    return (float)sqrt(((double)d[0] * d[0] + (double)d[1] * d[1]) + (double)d[2] * d[2]);
-}
-
 __global__ __launch_bounds__(256) void k_update_normal_and_depth(
     int npts, const float* __restrict__ pos, const int32_t* __restrict__ offs, const int32_t* __restrict__ obs_kf,
     const float* __restrict__ kf_Ow, int nkf, const int32_t* __restrict__ ref_kf,
@@ -134,18 +131,14 @@ __global__ __launch_bounds__(256) void k_update_normal_and_depth(
     for (int o = a; o < e; o++) {  // observation-map order (:302-309)
         const int kf = obs_kf[o];
         if (kf < 0 || kf >= nkf) return;
-        const float d[3] = {X[0] - kf_Ow[3 * kf], X[1] - kf_Ow[3 * kf + 1], X[2] - kf_Ow[3 * kf + 2]};
-        const float f = (float)(1.0 / (double)norm3(d));  // normali / cv::norm(normali): one float factor
-#pragma unroll
-        for (int c = 0; c < 3; c++) nr[c] = nr[c] + d[c] * f;
+        gfnd::add_view(X, kf_Ow + 3 * kf, nr);
     }
-    const float PC[3] = {X[0] - kf_Ow[3 * ref], X[1] - kf_Ow[3 * ref + 1], X[2] - kf_Ow[3 * ref + 2]};
-    const float dist = norm3(PC);
-    min_dist[p] = ((1.0f / sf) * dist) / fc.scales[level];          // :320
-    max_dist[p] = (sf * dist) * fc.scales[fc.nlevels - 1 - level];  // :321
-    const float fn = (float)(1.0 / (double)(e - a));                // normal / n (:322)
+    float nm[3], mn, mx;
+    gfnd::finish(X, kf_Ow + 3 * ref, nr, e - a, sf, fc.scales[level], fc.scales[fc.nlevels - 1 - level], nm, mn, mx);
+    min_dist[p] = mn;
+    max_dist[p] = mx;
 #pragma unroll
-    for (int c = 0; c < 3; c++) normal[3 * p + c] = nr[c] * fn;
+    for (int c = 0; c < 3; c++) normal[3 * p + c] = nm[c];
 }
 
 }  // namespace

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "cvsvd_core.h"
+#include "depthselect.h"
 
 namespace {
 
@@ -98,39 +99,12 @@ __global__ __launch_bounds__(NP_ST) void k_np_setup(NpCam cam, NpKf cur, const N
     for (int j = tid; j < n2; j += NP_ST) {
         const int m = K.mp[j];
         if (m < 0 || m >= nmp) continue;
-        const float* p = mp_pos + 3 * (size_t)m;
-        const double d = (double)K.Tcw[8] * (double)p[0] + (double)K.Tcw[9] * (double)p[1] +
-                         (double)K.Tcw[10] * (double)p[2];
-        keys[atomicAdd(&s_cnt, 1)] = ord_key((float)(d + (double)K.Tcw[11]));
+        keys[atomicAdd(&s_cnt, 1)] = ord_key(gfsel::scene_depth(K.Tcw, mp_pos + 3 * (size_t)m));
     }
     __syncthreads();
     const int nd = s_cnt;
-    if (nd > 0) {
-        // the element std::sort puts at (n-1)/2: radix select, 8 bits a pass
-        if (tid == 0) {
-            s_prefix = 0;
-            s_rank = (nd - 1) / 2;
-        }
-        for (int pass = 0; pass < 4; pass++) {
-            const int shift = 24 - 8 * pass;
-            const uint32_t mask = pass ? 0xffffffffu << (32 - 8 * pass) : 0u;
-            hist[tid] = 0;
-            __syncthreads();
-            const uint32_t pre = s_prefix;
-            for (int j = tid; j < nd; j += NP_ST) {
-                const uint32_t k = keys[j];
-                if ((k & mask) == pre) atomicAdd(&hist[(k >> shift) & 255], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int r = s_rank, d = 0;
-                while (d < 255 && r >= hist[d]) r -= hist[d++];
-                s_rank = r;
-                s_prefix = pre | ((uint32_t)d << shift);
-            }
-            __syncthreads();
-        }
-    }
+    // the element std::sort puts at (n-1)/2
+    if (nd > 0) gfsel::radix_select<NP_ST>(keys, nd, (nd - 1) / 2, hist, &s_prefix, &s_rank);
     if (tid != 0) return;
     gf_newpoints_neigh R;
     R.status = GF_NP_OK;

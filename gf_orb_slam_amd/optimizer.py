@@ -309,16 +309,86 @@ def local_bundle_adjustment(prob: dict, ctx=None, stop_flag=None):
     return arr.out()
 
 
+def bundle_adjustment(prob: dict, iterations: int, ctx=None, stop_flag=None):
+    """Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag)
+    (Optimizer.cc:36-142) on one graph (dict with the gf_ba_problem arrays):
+    one optimize(iterations), no outlier pass. stop_flag: optional
+    ctypes.c_uint8. Returns (kf_Tcw, pt_pos, edge_outlier (all zero),
+    iterations (run, -1))."""
+    ctx = ctx or default_context()
+    arr = BAArrays(prob)
+    check(lib().gf_bundle_adjustment(ctx.handle, ctypes.byref(arr.problem), int(iterations),
+                                     ctypes.byref(arr.result),
+                                     ctypes.byref(stop_flag) if stop_flag is not None else None))
+    return arr.out()
+
+
+def global_bundle_adjustment(map, iterations: int = 20, stop_flag=None, ctx=None) -> dict:
+    """Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag)
+    (Optimizer.cc:28-142) on a ``loopmap.LoopMap``. The graph is assembled on
+    the host (it runs once per map): the non-bad keyframes in index order
+    (fixed when mnId == 0), the non-bad points in id order, each point's
+    observations in keyframe-index order with bad keyframes skipped
+    (docs/ORACLE_ASSUMPTIONS.md A26). Solved by ``gf_bundle_adjustment``, which
+    raises above 32 free keyframes; the poses are written back with
+    ``set_pose``, the positions into ``map.mps`` and the points get the batched
+    UpdateNormalAndDepth (:139). -> dict: ``iterations`` (run; -1 when the
+    graph has no edge), ``keyframes`` and ``points``, the indices written."""
+    ctx = ctx or default_context()
+    kfs = [k for k in range(map.nkf) if not map.kf_bad[k]]
+    col = {k: j for j, k in enumerate(kfs)}
+    pts = [p for p in range(len(map.mps)) if not map.mp_bad[p]]
+    invs = inv_level_sigma2(map.info.nlevels, map.info.scale_factor)
+    e_pt, e_kf, e_z, e_w = [], [], [], []
+    for j, p in enumerate(pts):
+        for kf in sorted(map.obs[p]):
+            if kf not in col:
+                continue
+            kp = map.kf_kps[kf][map.obs[p][kf]]
+            e_pt.append(j)
+            e_kf.append(col[kf])
+            e_z.append((kp["x"], kp["y"]))
+            e_w.append(invs[int(kp["octave"])])
+    cam = np.array([map.info.fx, map.info.fy, map.info.cx, map.info.cy], np.float32)
+    prob = dict(kf_Tcw=np.asarray(map.Tcw, np.float32).reshape(-1, 16)[kfs].reshape(-1, 16),
+                kf_kind=np.asarray([BA_LOCAL_FIXED if map.kf_id[k] == 0 else BA_LOCAL for k in kfs], np.uint8),
+                kf_cam=np.tile(cam, (len(kfs), 1)), pt_pos=map.mps["pos"][pts].reshape(-1, 3),
+                edge_pt=np.asarray(e_pt, np.int32), edge_kf=np.asarray(e_kf, np.int32),
+                edge_z=np.asarray(e_z, np.float32).reshape(-1, 2), edge_inv_sigma2=np.asarray(e_w, np.float32))
+    T, X, _, its = bundle_adjustment(prob, iterations, ctx, stop_flag)
+    for j, k in enumerate(kfs):
+        map.set_pose(k, T[j])
+    if pts:
+        map.mps["pos"][pts] = X
+        map.update_normal_and_depth_batch(pts, ctx)
+    return dict(iterations=its[0], keyframes=kfs, points=pts)
+
+
 class LocalBAPlan:
     """Batched device path: nprob local windows uploaded once, solved together
-    (gf_ba_plan_create / _solve / _results)."""
+    (gf_ba_plan_create / _solve / _results). iterations=None: the
+    LocalBundleAdjustment schedule (optimize(5), outlier pass, optimize(10),
+    outlier pass); iterations=n: BundleAdjustment's one optimize(n) without
+    outlier passes (gf_ba_plan_create_iters)."""
 
-    def __init__(self, probs: list, ctx=None):
+    def __init__(self, probs: list, ctx=None, iterations=None):
         self.ctx = ctx or default_context()
         self.arrs = [BAArrays(p) for p in probs]
         ps = (BAProblem * len(probs))(*[a.problem for a in self.arrs])
         self.handle = ctypes.c_void_p()
-        check(lib().gf_ba_plan_create(self.ctx.handle, len(probs), ps, ctypes.byref(self.handle)))
+        if iterations is None:
+            check(lib().gf_ba_plan_create(self.ctx.handle, len(probs), ps, ctypes.byref(self.handle)))
+        else:
+            check(lib().gf_ba_plan_create_iters(self.ctx.handle, len(probs), ps, int(iterations),
+                                                ctypes.byref(self.handle)))
+
+    def results_dev(self, p: int):
+        """gf_ba_plan_results_dev: (kf_Tcw, pt_pos, iterations) device
+        addresses of problem p's outputs (nkf x 16 and npts x 3 floats, 2
+        int32), valid after solve() for work on the same stream."""
+        T, X, I = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().gf_ba_plan_results_dev(self.handle, int(p), ctypes.byref(T), ctypes.byref(X), ctypes.byref(I)))
+        return T.value, X.value, I.value
 
     def solve(self, stream=None) -> int:
         steps = ctypes.c_int()

@@ -1,0 +1,263 @@
+"""``Tracking::CreateInitialMap`` (src/Tracking.cc:1199-1322): the link from
+the monocular initialiser to a map that ``LocalMapper`` can take over.
+
+``create_initial_maps_device`` is the batched device path: stage 1
+(``gf_initial_map_points_dev``: the filter of Tracking.cc:1126-1133, the map
+points, the slot tables and the graph), ``Optimizer::GlobalBundleAdjustemnt(
+mpMap, 20)`` as a ``LocalBAPlan(iterations=20)`` and stage 2
+(``gf_initial_map_finish_dev``: UpdateNormalAndDepth, the median depth, the
+reset tests and the scaling), which reads the solver's output in place. It
+chains from ``initializer.initialize_batch_device`` without host work on the
+inputs; the graph arrays are downloaded once for the plan's constructor.
+``create_initial_map`` is a batch of one turned into a ``LoopMap``.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from ._lib import check, lib
+from .initializer import INIT_RESULT_DTYPE
+from .matcher import MAP_POINT_DTYPE, default_context
+from .orb import KEYPOINT_DTYPE
+
+GF_IM_OK, GF_IM_NOT_INITIALIZED, GF_IM_RESET_DEPTH, GF_IM_RESET_FEW = 0, 1, 2, 3
+STATUS_NAMES = {0: "GF_IM_OK", 1: "GF_IM_NOT_INITIALIZED", 2: "GF_IM_RESET_DEPTH", 3: "GF_IM_RESET_FEW"}
+THRES_INIT_MPT_NUM = 100  # include/Tracking.h
+INIT_BA_ITERATIONS = 20   # Tracking.cc:1263
+
+REPORT_DTYPE = np.dtype([("status", "i4"), ("npts", "i4"), ("tracked", "i4"), ("ba_iterations", "i4"),
+                         ("median_depth", "f4"), ("Tcw", "f4", (2, 4, 4))])
+assert REPORT_DTYPE.itemsize == 148
+
+_IN_PTRS = ("kps1", "desc1", "n1", "kps2", "desc2", "n2", "matches12", "init", "p3d", "triangulated")
+_PT_FIELDS = ("status", "npts", "pt_kp", "mps", "mp_desc", "slots1", "slots2", "kf_Tcw", "kf_kind", "kf_cam", "pt_pos",
+              "edge_pt", "edge_kf", "edge_z", "edge_inv_sigma2")
+
+
+class InitMapIn(ctypes.Structure):
+    """gf_initmap_in."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in _IN_PTRS] + [("cap1", ctypes.c_int32), ("cap2", ctypes.c_int32)]
+
+
+class InitMapPoints(ctypes.Structure):
+    """gf_initmap_points."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in _PT_FIELDS]
+
+
+def _alloc_points(P, cap1, cap2, dev):
+    import torch
+
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+    i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+    return dict(status=z(P, i32), npts=z(P, i32), pt_kp=z((P, cap1, 2), i32),
+                mps=z((P, cap1, MAP_POINT_DTYPE.itemsize), u8), mp_desc=z((P, cap1, 32), u8), slots1=z((P, cap1), i32),
+                slots2=z((P, cap2), i32), kf_Tcw=z((P, 2, 16), f32), kf_kind=z((P, 2), u8), kf_cam=z((P, 2, 4), f32),
+                pt_pos=z((P, cap1, 3), f32), edge_pt=z((P, 2 * cap1), i32), edge_kf=z((P, 2 * cap1), i32),
+                edge_z=z((P, 2 * cap1, 2), f32), edge_inv_sigma2=z((P, 2 * cap1), f32))
+
+
+def _stream(dev):
+    import torch
+
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def initial_map_points_device(info, kps1, desc1, n1, kps2, desc2, n2, matches12, init, p3d, triangulated, ctx=None):
+    """Stage 1 on device tensors laid out as ``initialize_batch_device`` lays
+    them out: kps1 [P, cap1, 28] / kps2 [P, cap2, 28] uint8, desc1 [P, cap1,
+    32] / desc2 uint8, n1 / n2 [P] int32, matches12 [P, cap1] int32, init
+    [P, 200] uint8, p3d [P, cap1, 3] f32, triangulated [P, cap1] uint8.
+    Enqueued on the current torch stream. -> (InitMapIn, dict of the device
+    outputs named as gf_initmap_points names them)."""
+    ctx = ctx or default_context()
+    P, cap1, cap2 = kps1.shape[0], kps1.shape[1], kps2.shape[1]
+    tens = dict(kps1=kps1, desc1=desc1, n1=n1, kps2=kps2, desc2=desc2, n2=n2, matches12=matches12, init=init, p3d=p3d,
+                triangulated=triangulated)
+    for k, t in tens.items():
+        if not t.is_contiguous() or t.shape[0] != P:
+            raise ValueError(f"{k}: a contiguous tensor with one row per problem")
+    arg = InitMapIn(*[tens[k].data_ptr() for k in _IN_PTRS], cap1, cap2)
+    arg._keep = tens
+    out = _alloc_points(P, cap1, cap2, kps1.device)
+    pts = InitMapPoints(*[out[k].data_ptr() for k in _PT_FIELDS])
+    check(lib().gf_initial_map_points_dev(ctx.handle, ctypes.byref(info), P, ctypes.byref(arg), ctypes.byref(pts),
+                                          _stream(kps1.device)))
+    return arg, out
+
+
+def initial_map_finish_device(info, arg, out, ba_Tcw_ptrs, ba_pos_ptrs, ba_iter_ptrs=None,
+                              thres: int = THRES_INIT_MPT_NUM, ctx=None):
+    """Stage 2: ``arg`` / ``out`` as stage 1 returned them; ba_*_ptrs: int64
+    device tensors [P] holding device addresses (per problem the optimised 2 x
+    16 poses, npts x 3 points, the iteration count). -> (report [P, 148] uint8,
+    mps [P, cap1, 32] uint8), device tensors."""
+    import torch
+
+    ctx = ctx or default_context()
+    dev = out["status"].device
+    P, cap1 = out["slots1"].shape
+    rep = torch.zeros((P, REPORT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    mps = torch.zeros((P, cap1, MAP_POINT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    pts = InitMapPoints(*[out[k].data_ptr() for k in _PT_FIELDS])
+    check(lib().gf_initial_map_finish_dev(ctx.handle, ctypes.byref(info), P, ctypes.byref(arg), ctypes.byref(pts),
+                                          ba_Tcw_ptrs.data_ptr(), ba_pos_ptrs.data_ptr(),
+                                          ba_iter_ptrs.data_ptr() if ba_iter_ptrs is not None else None, int(thres),
+                                          rep.data_ptr(), mps.data_ptr(), _stream(dev)))
+    return rep, mps
+
+
+def ba_problems(out: dict) -> list:
+    """The gf_ba_problem dicts of stage 1's output (one download)."""
+    h = {k: out[k].cpu().numpy() for k in ("npts", "kf_Tcw", "kf_kind", "kf_cam", "pt_pos", "edge_pt", "edge_kf",
+                                           "edge_z", "edge_inv_sigma2")}
+    probs = []
+    for p, n in enumerate(h["npts"]):
+        n = int(n)
+        probs.append(dict(kf_Tcw=h["kf_Tcw"][p], kf_kind=h["kf_kind"][p], kf_cam=h["kf_cam"][p],
+                          pt_pos=h["pt_pos"][p, :n], edge_pt=h["edge_pt"][p, :2 * n], edge_kf=h["edge_kf"][p, :2 * n],
+                          edge_z=h["edge_z"][p, :2 * n], edge_inv_sigma2=h["edge_inv_sigma2"][p, :2 * n]))
+    return probs
+
+
+def create_initial_maps_device(info, kps1, desc1, n1, kps2, desc2, n2, matches12, init, p3d, triangulated,
+                               thres: int = THRES_INIT_MPT_NUM, iterations: int = INIT_BA_ITERATIONS, ctx=None) -> dict:
+    """CreateInitialMap for a batch (tensors as in
+    :func:`initial_map_points_device`): stage 1, one
+    ``LocalBAPlan(iterations=20)`` over all problems (a failed initialisation
+    is an empty graph in it), stage 2 reading the plan's device results. All on
+    the current torch stream. -> dict of device tensors: ``report`` [P, 148]
+    uint8 (REPORT_DTYPE rows), ``mps`` [P, cap1, 32] uint8 (MAP_POINT_DTYPE
+    rows), and stage 1's ``npts``, ``pt_kp``, ``mp_desc``, ``slots1``,
+    ``slots2``; ``ba_steps``: the solver steps run; ``times``: host-clock
+    seconds of stage 1 with the graph download (``points``), the plan's
+    constructor (``plan``), the solve (``solve``) and stage 2 (``finish``)."""
+    import time
+
+    import torch
+
+    from .optimizer import LocalBAPlan
+
+    ctx = ctx or default_context()
+    dev = kps1.device
+    t = [time.perf_counter()]
+    times = {}
+
+    def lap(name):
+        t.append(time.perf_counter())
+        times[name] = t[-1] - t[-2]
+
+    arg, out = initial_map_points_device(info, kps1, desc1, n1, kps2, desc2, n2, matches12, init, p3d, triangulated,
+                                         ctx)
+    probs = ba_problems(out)
+    lap("points")
+    plan = LocalBAPlan(probs, ctx, iterations=iterations)
+    lap("plan")
+    try:
+        steps = plan.solve(_stream(dev))
+        lap("solve")
+        ptrs = np.asarray([plan.results_dev(p) for p in range(len(plan.arrs))], np.int64).reshape(-1, 3)
+        tabs = torch.from_numpy(np.ascontiguousarray(ptrs.T)).to(dev)
+        rep, mps = initial_map_finish_device(info, arg, out, tabs[0], tabs[1], tabs[2], thres, ctx)
+        torch.cuda.current_stream(dev).synchronize()  # the plan's arrays are read until here
+        lap("finish")
+    finally:
+        plan.close()
+    return dict(report=rep, mps=mps, npts=out["npts"], pt_kp=out["pt_kp"], mp_desc=out["mp_desc"],
+                slots1=out["slots1"], slots2=out["slots2"], ba_steps=steps, times=times)
+
+
+def _dev_inputs(kps1, desc1, kps2, desc2, matches12, init, p3d, triangulated, device="cuda"):
+    """One host problem as the batch-of-one device tensors."""
+    import torch
+
+    k1, k2 = np.ascontiguousarray(kps1, KEYPOINT_DTYPE), np.ascontiguousarray(kps2, KEYPOINT_DTYPE)
+    n1, n2 = len(k1), len(k2)
+    if n1 > 4096 or n2 > 4096:
+        raise ValueError("a frame holds at most 4096 keypoints")
+    c1, c2 = max(n1, 1), max(n2, 1)
+    if not (np.size(matches12) == n1 and np.size(p3d) == 3 * n1 and np.size(triangulated) == n1 and
+            np.size(desc1) == 32 * n1 and np.size(desc2) == 32 * n2):
+        raise ValueError("matches12, p3d, triangulated and the descriptors: one row per keypoint")
+
+    def up(a, shape, dt):
+        buf = np.zeros(shape, dt)
+        a = np.ascontiguousarray(a, dt).reshape(-1)
+        buf.reshape(-1)[:a.size] = a
+        return torch.from_numpy(buf).to(device)
+
+    return (up(k1.view(np.uint8), (1, c1, 28), np.uint8),
+            up(np.ascontiguousarray(desc1, np.uint8), (1, c1, 32), np.uint8),
+            torch.tensor([n1], dtype=torch.int32, device=device),
+            up(k2.view(np.uint8), (1, c2, 28), np.uint8),
+            up(np.ascontiguousarray(desc2, np.uint8), (1, c2, 32), np.uint8),
+            torch.tensor([n2], dtype=torch.int32, device=device),
+            up(np.ascontiguousarray(matches12, np.int32), (1, c1), np.int32),
+            up(np.ascontiguousarray(np.asarray(init).reshape(-1)[:1], INIT_RESULT_DTYPE).view(np.uint8), (1, 200), np.uint8),
+            up(np.ascontiguousarray(p3d, np.float32), (1, c1, 3), np.float32),
+            up(np.ascontiguousarray(np.asarray(triangulated).astype(np.uint8)), (1, c1), np.uint8))
+
+
+def create_initial_map(info, K, kps1, desc1, kps2, desc2, matches12, init_result, p3d, triangulated, voc=None,
+                       ctx=None, thres: int = THRES_INIT_MPT_NUM, levelsup: int = 4):
+    """Tracking::CreateInitialMap on one initialiser output (host arrays:
+    undistorted keypoints and [n, 32] descriptors of the two frames,
+    mvIniMatches, the INIT_RESULT_DTYPE record, vP3D, vbTriangulated) ->
+    ``(LoopMap | None, report)``.
+
+    The map has keyframes 0 (KFini, mnId 0, identity) and 1 (KFcur, mnId 1),
+    the points in index order of their KFini keypoint with ``ref_kf`` 1 and
+    observations ``{0: i, 1: matches12[i]}``, both slot tables,
+    ``ComputeBoW`` of both keyframes when ``voc`` is given (an
+    ``ORBVocabulary`` or a callable, as ``process_new_keyframe`` takes it) and
+    ``UpdateConnections`` of both (:1254-1255), median depth 1. ``None`` where
+    the reference calls ``Reset()`` (or the initialiser had failed); report:
+    dict with ``status`` (GF_IM_*), ``npts``, ``tracked``, ``ba_iterations``,
+    ``median_depth``, ``Tcw`` [2, 4, 4] and ``times`` (host-clock seconds:
+    ``upload``, the laps of :func:`create_initial_maps_device`, ``map`` for
+    the download and the LoopMap, ``bow``, ``connections``). K is the calibration the
+    initialiser ran with; the map's camera is ``info``'s."""
+    from .bow import FeatureVector
+    from .loopmap import LoopMap
+
+    ctx = ctx or default_context()
+    Kf = np.asarray(K, np.float32).reshape(3, 3)
+    if not (Kf[0, 0] == np.float32(info.fx) and Kf[1, 1] == np.float32(info.fy) and Kf[0, 2] == np.float32(info.cx)
+            and Kf[1, 2] == np.float32(info.cy)):
+        raise ValueError("K and info describe different cameras")
+    import time
+
+    t0 = time.perf_counter()
+    tens = _dev_inputs(kps1, desc1, kps2, desc2, matches12, init_result, p3d, triangulated)
+    t1 = time.perf_counter()
+    res = create_initial_maps_device(info, *tens, thres=thres, ctx=ctx)
+    t2 = time.perf_counter()
+    r = res["report"].cpu().numpy().view(REPORT_DTYPE)[0, 0]
+    times = dict(upload=t1 - t0, **res["times"])
+    report = dict(status=int(r["status"]), npts=int(r["npts"]), tracked=int(r["tracked"]),
+                  ba_iterations=int(r["ba_iterations"]), median_depth=np.float32(r["median_depth"]),
+                  Tcw=r["Tcw"].copy(), times=times)
+    if report["status"] != GF_IM_OK:
+        return None, report
+    n, n1, n2 = report["npts"], len(kps1), len(kps2)
+    mps = res["mps"].cpu().numpy().reshape(-1).view(MAP_POINT_DTYPE)[:n].copy()
+    pt_kp = res["pt_kp"].cpu().numpy()[0, :n]
+    m = LoopMap(info, [kps1, kps2], [desc1, desc2],
+                [res["slots1"].cpu().numpy()[0, :n1], res["slots2"].cpu().numpy()[0, :n2]], mps,
+                res["mp_desc"].cpu().numpy()[0, :n], observations=[{0: int(a), 1: int(b)} for a, b in pt_kp],
+                kf_Tcw=report["Tcw"], ref_kf=np.ones(n, np.int32), kf_id=[0, 1])
+    t3 = time.perf_counter()
+    times["map"] = t3 - t2
+    if voc is not None:
+        transform = voc.transform if hasattr(voc, "transform") else voc
+        for k in (0, 1):
+            words, values, fv = transform(m.kf_desc[k], levelsup)
+            m.kf_bow[k] = (words, values)
+            m.kf_fv[k] = fv if isinstance(fv, FeatureVector) else FeatureVector(*fv)
+    t4 = time.perf_counter()
+    m.update_connections_batch([0, 1], ctx)
+    times["bow"], times["connections"] = t4 - t3, time.perf_counter() - t4
+    return m, report

@@ -559,6 +559,34 @@ int gf_ba_plan_solve_stop(gf_ba_plan* plan, void* stream, const volatile uint8_t
 int gf_local_ba_stop(gf_ctx* ctx, const gf_ba_problem* prob, gf_ba_result* res, const volatile uint8_t* stop_flag);
 int gf_ba_plan_destroy(gf_ba_plan* plan);
 
+/* Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag)
+ * (src/Optimizer.cc:36-142; GlobalBundleAdjustemnt :28-33 calls it on the
+ * whole map) on the same graph arrays: one optimize(niterations), no outlier
+ * pass and no edge removal. The solver's schedule (the iteration caps of the
+ * two optimize() calls, whether the outlier passes run) is a property of the
+ * plan: gf_ba_plan_create builds the local form's {5, 10} with the passes,
+ * gf_ba_plan_create_iters {niterations} without them; the solve and results
+ * entries above serve both. Results: edge_outlier all zero, iterations =
+ * {run, -1}; a graph without an edge has nothing to optimise (initialize-
+ * Optimization fails): {-1, -1}, inputs returned. All three kf_kind values
+ * are accepted (BundleAdjustment itself makes 0 and, for mnId == 0, 1).
+ * niterations in [0, 64], else GF_ERR_ARG; the limits of the local form hold
+ * (GF_ERR_UNSUPPORTED beyond them). stop_flag as in gf_local_ba_stop: raised,
+ * optimize() ends at its next iteration boundary. The host loop gives up
+ * with an error after 10 * niterations + 1 steps (an iteration takes at most
+ * 10 LM trials, one step each). */
+int gf_ba_plan_create_iters(gf_ctx* ctx, int nprob, const gf_ba_problem* probs, int niterations, gf_ba_plan** out);
+int gf_bundle_adjustment(gf_ctx* ctx, const gf_ba_problem* prob, int niterations, gf_ba_result* res,
+                         const volatile uint8_t* stop_flag);
+/* Device pointers into the plan's output arrays for problem p (Optimizer.cc:
+ * 125-140, the recovered poses and points): kf_Tcw nkf x 16 and pt_pos npts x
+ * 3 floats, the values gf_ba_plan_results copies out, and iterations, the two
+ * counts of gf_ba_result. Valid after a solve for work enqueued on the same
+ * stream, until the next solve or the plan's destruction; any output pointer
+ * may be NULL. */
+int gf_ba_plan_results_dev(gf_ba_plan* plan, int p, const float** kf_Tcw, const float** pt_pos,
+                           const int32_t** iterations);
+
 /* ------------------------------------------------ keypoint undistortion
  * Frame::UndistortKeyPoints (Frame.cc:389-423): cv::undistortPoints with
  * K = {fx, fy, cx, cy} and dist = {k1, k2, p1, p2, k3} (k3 = 0 for the 4-term
@@ -1477,6 +1505,105 @@ int gf_initialize_batch_dev(gf_ctx* ctx, int nprob, const float K[9], float sigm
                             const gf_keypoint* d_kps2, int cap2, const int32_t* d_n2, const int32_t* d_matches12,
                             gf_rng* d_rng, gf_init_result* d_result, float* d_p3d, uint8_t* d_triangulated,
                             void* stream);
+
+/* ------------------------------------------------ the initial map
+ * Tracking::CreateInitialMap (src/Tracking.cc:1199-1322) behind the filter of
+ * Tracking::Initialize (:1126-1133), as two batched device stages around the
+ * bundle adjustment (gf_ba_plan_create_iters with 20 iterations, :1263). The
+ * inputs are laid out as gf_initialize_batch_dev lays them out, [P][cap...]
+ * with per-problem counts (clamped to the caps); a frame holds at most 4096
+ * keypoints. Descriptors are 32 bytes a row and 4-byte aligned. KFcur's pose
+ * is [R21 | t21] as the initialiser returned them (the motion-prior rescale of
+ * :1139 belongs to Tracking::Initialize's bookkeeping and is not applied). */
+enum {
+    GF_IM_OK = 0,
+    GF_IM_NOT_INITIALIZED = 1, /* the initialiser's record says ok == 0: no map, nothing to reset */
+    GF_IM_RESET_DEPTH = 2,     /* medianDepth < 0: the reference calls Reset() (:1269) */
+    GF_IM_RESET_FEW = 3        /* TrackedMapPoints() < THRES_INIT_MPT_NUM, or no point at all */
+};
+
+typedef struct gf_initmap_in { /* device pointers */
+    const gf_keypoint* kps1;     /* [P][cap1] KFini's undistorted keypoints            */
+    const uint8_t* desc1;        /* [P][cap1][32]                                      */
+    const int32_t* n1;           /* [P]                                                */
+    const gf_keypoint* kps2;     /* [P][cap2] KFcur's                                  */
+    const uint8_t* desc2;        /* [P][cap2][32]                                      */
+    const int32_t* n2;           /* [P]                                                */
+    const int32_t* matches12;    /* [P][cap1] mvIniMatches before the filter           */
+    const gf_init_result* init;  /* [P] the initialiser's records                      */
+    const float* p3d;            /* [P][cap1][3] mvIniP3D                              */
+    const uint8_t* triangulated; /* [P][cap1] vbTriangulated                           */
+    int32_t cap1, cap2;
+} gf_initmap_in;
+
+/* What gf_initial_map_points_dev writes (device pointers). The last nine
+ * arrays are problem p's gf_ba_problem in the orders that struct demands:
+ * nkf = 2, npts = npts[p], nedges = 2 npts[p]. */
+typedef struct gf_initmap_points {
+    int32_t* status;        /* [P] GF_IM_OK or GF_IM_NOT_INITIALIZED                         */
+    int32_t* npts;          /* [P]                                                           */
+    int32_t* pt_kp;         /* [P][cap1][2] the observations: keypoint in KFini, in KFcur    */
+    gf_map_point* mps;      /* [P][cap1]                                                     */
+    uint8_t* mp_desc;       /* [P][cap1][32]                                                 */
+    int32_t* slots1;        /* [P][cap1] KFini's mvpMapPoints, -1 = NULL                     */
+    int32_t* slots2;        /* [P][cap2] KFcur's                                             */
+    float* kf_Tcw;          /* [P][2][16] KFini identity, KFcur [R21 | t21]                  */
+    uint8_t* kf_kind;       /* [P][2] 1 (fixed, mnId 0), 0                                   */
+    float* kf_cam;          /* [P][2][4]                                                     */
+    float* pt_pos;          /* [P][cap1][3]                                                  */
+    int32_t* edge_pt;       /* [P][2 cap1] edge 2j and 2j + 1: point j                       */
+    int32_t* edge_kf;       /* [P][2 cap1] 0 (KFini), 1 (KFcur)                              */
+    float* edge_z;          /* [P][2 cap1][2] the undistorted keypoint position              */
+    float* edge_inv_sigma2; /* [P][2 cap1] GetInvSigma2(octave)                              */
+} gf_initmap_points;
+
+/* Stage 1 (:1126-1133, :1206-1249). A problem whose record says ok == 0 gets
+ * zero points, empty slot tables and GF_IM_NOT_INITIALIZED. Otherwise the
+ * matches with matches12[i] >= 0 && triangulated[i] (and matches12[i] <
+ * n2[p]: the reference would index outside the frame) become the map points
+ * 0..n-1 in increasing i. Per point: the keypoint pair; the position p3d[i];
+ * the descriptor, ComputeDistinctiveDescriptors over two observations =
+ * KFini's row (both medians are 0, the first observation wins); normal and
+ * min / max distance by UpdateNormalAndDepth with mpRefKF = pKFcur (level =
+ * the octave of the KFcur keypoint), KFini at identity and KFcur at [R21 |
+ * t21], in the arithmetic of gf_update_normal_and_depth. Slot tables: when
+ * two matches name the same KFcur keypoint the later i owns the slot, as
+ * AddMapPoint overwrites; both points keep their observation. */
+int gf_initial_map_points_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, const gf_initmap_in* in,
+                              const gf_initmap_points* out, void* stream);
+
+typedef struct gf_initmap_report {
+    int32_t status;        /* GF_IM_*                                                     */
+    int32_t npts;          /* map points                                                  */
+    int32_t tracked;       /* pKFcur->TrackedMapPoints(): its non-NULL slots               */
+    int32_t ba_iterations; /* iterations of optimize(20), -1 = not run                    */
+    float median_depth;    /* pKFini->ComputeSceneMedianDepth(2) before the scaling       */
+    float Tcw[32];         /* KFini, KFcur: final poses, row-major 4x4 each               */
+} gf_initmap_report;
+
+/* Stage 2 (Optimizer.cc:125-140, Tracking.cc:1268-1299) from the solver's
+ * output, read in place: d_ba_kf_Tcw[p] / d_ba_pt_pos[p] are device pointers
+ * to problem p's optimised poses (2 x 16) and points (npts x 3), e.g. those
+ * of gf_ba_plan_results_dev, d_ba_iterations[p] a device pointer to its
+ * iteration count (the table may be NULL); the three tables themselves are
+ * device arrays of nprob pointers. Every point gets
+ * UpdateNormalAndDepth with the optimised pose and positions; the median
+ * depth is the element (n - 1) / 2 of KFini's sorted depths z = (float)
+ * (Rcw.row(2) . x + zcw), by an exact selection; status GF_IM_RESET_DEPTH
+ * when it is < 0, else GF_IM_RESET_FEW when tracked < thres_init_mpt_num
+ * (THRES_INIT_MPT_NUM, 100 in the reference) or when there is no point at all
+ * (the reference indexes an empty vector there). On GF_IM_OK KFcur's
+ * translation and every point position are multiplied by invMedianDepth =
+ * 1.0f / median in float. The normals and the min / max distances are NOT
+ * recomputed after the scaling: they stay those of the unscaled result, as
+ * in the reference. On a reset status poses and points are the unscaled
+ * solver output. A GF_IM_NOT_INITIALIZED problem passes through (its BA
+ * pointers are not read). d_mps: [P][cap1] rows out. */
+int gf_initial_map_finish_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, const gf_initmap_in* in,
+                              const gf_initmap_points* pts, const float* const* d_ba_kf_Tcw,
+                              const float* const* d_ba_pt_pos, const int32_t* const* d_ba_iterations,
+                              int thres_init_mpt_num,
+                              gf_initmap_report* d_report, gf_map_point* d_mps, void* stream);
 
 /* ------------------------------------------------ tracking glue (device)
  * Per-frame bookkeeping of Tracking between the stages above, so a front-end

@@ -353,6 +353,14 @@ public:
         int iterations[2] = {0, 0};
     };
     static void LocalBundleAdjustment(LocalBAWindow* pWindow, bool* pbStopFlag);
+
+    /* Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag)
+     * (Optimizer.cc:36-142), the body of GlobalBundleAdjustemnt: the graph of
+     * :51-115 (every keyframe, fixed when mnId == 0, kinds 0 / 1; every point;
+     * each point's observations) in the same window type, one
+     * optimize(nIterations) without outlier pass. edge_outlier comes back all
+     * zero and iterations = {run, -1}. nIterations in [0, 64]. */
+    static void BundleAdjustment(LocalBAWindow* pWindow, int nIterations, bool* pbStopFlag = nullptr);
 };
 
 }  // namespace ORB_SLAM
