@@ -144,6 +144,15 @@ all: $(INITMAPREF)
 $(INITMAPREF): tests/helpers/initmap_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of ORBmatcher::SearchForInitialization over
+# Frame::GetFeaturesInArea and of the gate of Tracking::Initialize
+# (tests/test_searchinit_cpu.py, tests/test_searchinit_gpu.py,
+# tests/test_tracking_init_gpu.py), same flags
+SEARCHINITREF = tests/helpers/libsearchinitref.so
+all: $(SEARCHINITREF)
+$(SEARCHINITREF): tests/helpers/searchinit_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)
@@ -160,6 +169,12 @@ $(SEQDRV): tests/cpp/sequence_driver.cpp include/gfslam/orbslam.h include/gfslam
 BADRV = tests/cpp/ba_driver
 all: $(BADRV)
 $(BADRV): tests/cpp/ba_driver.cpp include/gfslam/orbslam.h include/gfslam/abi.h $(LIB)
+	$(CXX) -O2 -std=c++17 -Iinclude $< -Lgf_orb_slam_amd -lgfslam -Wl,-rpath,'$$ORIGIN/../../gf_orb_slam_amd' -o $@
+
+# drop-in ORBmatcher::SearchForInitialization caller (tests/test_searchinit_dropin_gpu.py)
+SIDRV = tests/cpp/searchinit_driver
+all: $(SIDRV)
+$(SIDRV): tests/cpp/searchinit_driver.cpp include/gfslam/orbslam.h include/gfslam/abi.h $(LIB)
 	$(CXX) -O2 -std=c++17 -Iinclude $< -Lgf_orb_slam_amd -lgfslam -Wl,-rpath,'$$ORIGIN/../../gf_orb_slam_amd' -o $@
 
 # diagnostic build: k_active_match phase stamps (scripts/am_stamps.py), never the product

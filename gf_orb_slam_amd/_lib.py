@@ -273,6 +273,10 @@ _PROTOS = {
     "gf_initialize": [_P, _P, _F, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     "gf_initialize_dev": [_P, _P, _F, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "gf_initialize_batch_dev": [_P, _I, _P, _F, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "gf_search_for_initialization": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P, _P],
+    "gf_search_for_initialization_batch_dev": [_P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _F, _I, _I, _P, _P, _P,
+                                               _P],
+    "gf_tracking_initialize_gate_dev": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

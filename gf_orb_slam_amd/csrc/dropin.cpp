@@ -292,6 +292,23 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
     return n;
 }
 
+int ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, std::vector<Point2f>& vbPrevMatched,
+                                        std::vector<int>& vnMatches12, int windowSize) {
+    if ((int)vbPrevMatched.size() != F1.N) throw GpuError(GF_ERR_ARG, "vbPrevMatched needs one entry per keypoint of F1");
+    static_assert(sizeof(Point2f) == 2 * sizeof(float), "Point2f must be two floats");
+    std::vector<int32_t> m12(F1.N > 0 ? F1.N : 1, -1);
+    const gf_frame_info fi = F2.info();
+    int n = 0;
+    check(gf_search_for_initialization(Context(), &fi, reinterpret_cast<const gf_keypoint*>(F1.mvKeysUn.data()),
+                                       F1.mDescriptors.data.data(), F1.N,
+                                       reinterpret_cast<const gf_keypoint*>(F2.mvKeysUn.data()),
+                                       F2.mDescriptors.data.data(), F2.N, windowSize, mfNNratio,
+                                       mbCheckOrientation ? 1 : 0, 0, reinterpret_cast<float*>(vbPrevMatched.data()),
+                                       m12.data(), &n));
+    vnMatches12.assign(m12.begin(), m12.begin() + F1.N);
+    return n;
+}
+
 int ORBmatcher::SearchByProjection_OnePoint(Frame& F, MapPoint* pMP, const float th) {
     if (!pMP || !pMP->mbTrackInView || pMP->isBad()) return -1;  // ORBmatcher.h:75-79
     PointTable T;

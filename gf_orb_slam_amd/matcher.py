@@ -22,6 +22,7 @@ FUSE_SEARCH_RESULT_DTYPE = np.dtype([("kp", "<i4"), ("dist", "<i4")])
 FUSE_SEARCH_CHUNK_DEFAULT = 256  # candidates per workgroup of gf_fuse_search_dev (csrc/neighbors.hip)
 MP_VIEW_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("view_cos", "<f4"), ("level", "<i4"), ("in_view", "<i4")])
 assert MAP_POINT_DTYPE.itemsize == 32 and MP_VIEW_DTYPE.itemsize == 20
+GF_SI_DIRECT = 1  # gf_search_for_initialization flag: every query walks its window in the ordered pass
 
 
 class FrameInfo(ctypes.Structure):
@@ -202,7 +203,27 @@ class ORBmatcher:
         i1 = np.nonzero(out >= 0)[0].astype(np.int32)
         return nm.value, out, np.stack([i1, out[i1]], 1)
 
-    def SearchByProjectionLast(self, CurrentFrame: Frame, LastFrame: Frame, th: float) -> int:
+    def SearchForInitialization(self, F1: Frame, F2: Frame, vbPrevMatched: np.ndarray, windowSize: int = 10,
+                                flags: int = 0):
+        """ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched,
+        vnMatches12, windowSize) (ORBmatcher.cc:1172-1287) over
+        ``gf_search_for_initialization``. vbPrevMatched: float32 [F1.N, 2],
+        C-contiguous, updated in place. -> (nmatches, vnMatches12 [F1.N]).
+        flags: ``GF_SI_DIRECT`` walks every window inside the ordered pass."""
+        prev = vbPrevMatched
+        if not (isinstance(prev, np.ndarray) and prev.dtype == np.float32 and prev.flags.c_contiguous and
+                prev.size == 2 * F1.N):
+            raise ValueError("vbPrevMatched: a C-contiguous float32 array [F1.N, 2]")
+        m12 = np.full(max(F1.N, 1), -1, np.int32)
+        n = ctypes.c_int()
+        check(lib().gf_search_for_initialization(
+            self.ctx.handle, ctypes.byref(F2.info), ptr(F1.mvKeysUn) if F1.N else None,
+            ptr(F1.mDescriptors) if F1.N else None, F1.N, ptr(F2.mvKeysUn) if F2.N else None,
+            ptr(F2.mDescriptors) if F2.N else None, F2.N, int(windowSize), ctypes.c_float(self.mfNNratio),
+            int(self.mbCheckOrientation), int(flags), ptr(prev) if F1.N else None, ptr(m12), ctypes.byref(n)))
+        return n.value, m12[:F1.N]
+
+    def SearchByProjectionLast(self,CurrentFrame: Frame, LastFrame: Frame, th: float) -> int:
         """ORBmatcher::SearchByProjection(Frame& Cur, const Frame& Last, th) (ORBmatcher.cc:2081)."""
         n = ctypes.c_int()
         check(lib().gf_match_lastframe(self.ctx.handle, ctypes.byref(CurrentFrame.info), ptr(CurrentFrame.mvKeysUn),

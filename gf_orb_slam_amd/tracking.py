@@ -10,6 +10,14 @@ reset tests and the scaling), which reads the solver's output in place. It
 chains from ``initializer.initialize_batch_device`` without host work on the
 inputs; the graph arrays are downloaded once for the plan's constructor.
 ``create_initial_map`` is a batch of one turned into a ``LoopMap``.
+
+Before it, ``Tracking::FirstInitialization`` / ``Tracking::Initialize``
+(Tracking.cc:920-946, 988-1040, Struct_Motion): ``search_gate_initialize_device``
+runs ORBmatcher::SearchForInitialization, the gate of :999-1017 and
+``Initializer::Initialize`` for P sequences on device tensors without a host
+step in between, ``initialize_device`` adds CreateInitialMap, and
+``MonoInitializer`` is the state machine of Tracking.cc:547-569 for one
+sequence, from extracted frames to a ``LoopMap``.
 """
 from __future__ import annotations
 
@@ -261,3 +269,182 @@ def create_initial_map(info, K, kps1, desc1, kps2, desc2, matches12, init_result
     m.update_connections_batch([0, 1], ctx)
     times["bow"], times["connections"] = t4 - t3, time.perf_counter() - t4
     return m, report
+
+
+# ------------------------------------------------ Tracking::Initialize
+GF_SI_OK, GF_SI_FEW_KEYPOINTS, GF_SI_FEW_MATCHES = 0, 1, 2
+SRH_WINDOW_SIZE_INIT = 100  # include/Tracking.h
+NOT_INITIALIZED, INITIALIZING, WORKING = "NOT_INITIALIZED", "INITIALIZING", "WORKING"
+
+
+def search_for_initialization_device(info, kps1, desc1, n1, kps2, desc2, n2, prev_matched,
+                                     window: int = SRH_WINDOW_SIZE_INIT, nnratio: float = 0.9, check_ori: bool = True,
+                                     flags: int = 0, ctx=None):
+    """``gf_search_for_initialization_batch_dev`` on device tensors laid out
+    as :func:`initial_map_points_device` takes them; prev_matched [P, cap1, 2]
+    f32 is updated in place. -> (matches12 [P, cap1] int32, nmatches [P]
+    int32). Enqueued on the current torch stream."""
+    import torch
+
+    ctx = ctx or default_context()
+    P, cap1, cap2 = kps1.shape[0], kps1.shape[1], kps2.shape[1]
+    for k, t in dict(kps1=kps1, desc1=desc1, n1=n1, kps2=kps2, desc2=desc2, n2=n2, prev_matched=prev_matched).items():
+        if not t.is_contiguous() or t.shape[0] != P:
+            raise ValueError(f"{k}: a contiguous tensor with one row per problem")
+    if prev_matched.dtype != torch.float32 or prev_matched.numel() != 2 * P * cap1:
+        raise ValueError("prev_matched: float32 [P, cap1, 2]")
+    dev = kps1.device
+    m12 = torch.empty((P, cap1), dtype=torch.int32, device=dev)
+    nm = torch.zeros(P, dtype=torch.int32, device=dev)
+    check(lib().gf_search_for_initialization_batch_dev(
+        ctx.handle, ctypes.byref(info), P, kps1.data_ptr(), desc1.data_ptr(), cap1, n1.data_ptr(), kps2.data_ptr(),
+        desc2.data_ptr(), cap2, n2.data_ptr(), int(window), ctypes.c_float(nnratio), int(bool(check_ori)), int(flags),
+        prev_matched.data_ptr(), m12.data_ptr(), nm.data_ptr(), _stream(dev)))
+    return m12, nm
+
+
+def search_gate_initialize_device(info, K, kps1, desc1, n1, kps2, desc2, n2, prev_matched, rng_states,
+                                  thres: int = THRES_INIT_MPT_NUM, flags: int = 0, ctx=None) -> dict:
+    """Tracking::Initialize (Tracking.cc:999-1023) for P sequences in one set
+    of launches: the matcher with ORBmatcher(0.9, true) and window 100, the
+    gate, ``Initializer(frame, 1.0, 200)::Initialize`` on each problem's own
+    rand() state (rng_states [P, 132] uint8, advanced in place where the
+    initialiser runs). prev_matched [P, cap1, 2] is updated in place as the
+    reference updates mvbPrevMatched. -> dict of device tensors: ``status``
+    (GF_SI_*), ``nmatches``, ``matches12`` (mvIniMatches as the matcher or the
+    gate left them), ``init_matches12`` (what the initialiser saw), ``init``
+    [P, 200] uint8, ``p3d``, ``triangulated``."""
+    import torch
+
+    from .initializer import initialize_batch_device
+
+    ctx = ctx or default_context()
+    dev = kps1.device
+    P, cap1 = kps1.shape[0], kps1.shape[1]
+    before = prev_matched.clone()
+    m12, nm = search_for_initialization_device(info, kps1, desc1, n1, kps2, desc2, n2, prev_matched, flags=flags,
+                                               ctx=ctx)
+    status = torch.zeros(P, dtype=torch.int32, device=dev)
+    init_m = torch.empty((P, cap1), dtype=torch.int32, device=dev)
+    check(lib().gf_tracking_initialize_gate_dev(ctx.handle, P, n2.data_ptr(), cap1, int(thres), before.data_ptr(),
+                                                prev_matched.data_ptr(), m12.data_ptr(), nm.data_ptr(),
+                                                status.data_ptr(), init_m.data_ptr(), _stream(dev)))
+    res, p3d, tri = initialize_batch_device(ctx, K, kps1, n1, kps2, n2, init_m, rng_states)
+    return dict(status=status, nmatches=nm, matches12=m12, init_matches12=init_m, init=res, p3d=p3d, triangulated=tri,
+                _keep=before)
+
+
+def initialize_device(info, K, kps1, desc1, n1, kps2, desc2, n2, prev_matched, rng_states,
+                      thres: int = THRES_INIT_MPT_NUM, flags: int = 0, ctx=None) -> dict:
+    """The batched chain search -> gate -> Initializer -> CreateInitialMap on
+    device tensors (see :func:`search_gate_initialize_device` and
+    :func:`create_initial_maps_device`). -> the dicts of both merged, plus
+    ``states``: per problem NOT_INITIALIZED (the gate failed or CreateInitialMap
+    reset), INITIALIZING (the initialiser failed) or WORKING, and
+    ``ini_matches`` [P, cap1] int32: mvIniMatches after the untriangulated
+    filter of Tracking.cc:1025-1032 where the initialiser succeeded."""
+    import torch
+
+    a = search_gate_initialize_device(info, K, kps1, desc1, n1, kps2, desc2, n2, prev_matched, rng_states, thres,
+                                      flags, ctx)
+    b = create_initial_maps_device(info, kps1, desc1, n1, kps2, desc2, n2, a["init_matches12"], a["init"], a["p3d"],
+                                   a["triangulated"], thres=thres, ctx=ctx)
+    ok = a["init"].view(torch.int32)[:, 0] != 0
+    m = a["matches12"]
+    drop = ok[:, None] & (m >= 0) & (a["triangulated"] == 0)
+    ini = torch.where(drop, torch.full_like(m, -1), m)
+    st = a["status"].cpu().numpy()
+    im = b["report"].cpu().numpy().view(REPORT_DTYPE).reshape(-1)["status"]
+    okh = ok.cpu().numpy()
+    states = [NOT_INITIALIZED if s != GF_SI_OK else INITIALIZING if not o else WORKING if i == GF_IM_OK
+              else NOT_INITIALIZED for s, o, i in zip(st, okh, im)]
+    return dict(a, **b, states=states, ini_matches=ini)
+
+
+class MonoInitializer:
+    """The tracker's start for one monocular sequence (Tracking.cc:547-569):
+    NOT_INITIALIZED -> FirstInitialization (:920-946), INITIALIZING ->
+    Initialize (:988-1040, Struct_Motion), WORKING once CreateInitialMap has
+    made a map. ``feed(kps, desc)`` takes one extracted frame (undistorted
+    keypoints, [n, 32] descriptors) and returns ``(state, map, report)``: the
+    ``LoopMap`` and CreateInitialMap's report when the state became WORKING,
+    else ``None`` and a dict with what was reached (``status`` of the gate,
+    ``nmatches``, ``init`` the initialiser's record, ``im_status``). A reset
+    status of CreateInitialMap returns the tracker to NOT_INITIALIZED, where
+    Reset() leaves mState (:4092); a failed initialiser leaves INITIALIZING
+    with mvbPrevMatched as the matcher updated it. ``rng`` is the caller's
+    rand() state (a ``pnp.Rand`` or its RNG_DTYPE record), advanced in place."""
+
+    def __init__(self, info, K, rng, voc=None, ctx=None, thres: int = THRES_INIT_MPT_NUM, levelsup: int = 4):
+        self.info, self.K, self.voc = info, np.asarray(K, np.float32).reshape(3, 3), voc
+        self.rng_state = rng.state if hasattr(rng, "state") else rng  # RNG_DTYPE [1], advanced in place
+        self.ctx = ctx or default_context()
+        self.thres, self.levelsup = int(thres), int(levelsup)
+        self.mState = NOT_INITIALIZED
+        self.mInitialFrame = None    # (keypoints, descriptors)
+        self.mvbPrevMatched = None   # float32 [n1, 2]
+        self.mvIniMatches = None     # int32 [n1]
+        self.times = {}
+
+    def feed(self, kps, desc):
+        import time
+
+        import torch
+
+        k = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(len(k), 32)
+        if len(k) > 4096:
+            raise ValueError("a frame holds at most 4096 keypoints")
+        if self.mState == WORKING:
+            raise RuntimeError("the map exists: the frame belongs to the tracking front end")
+        if self.mState == NOT_INITIALIZED:  # FirstInitialization
+            if len(k) > self.thres:
+                self.mInitialFrame = (k, d)
+                self.mvbPrevMatched = np.ascontiguousarray(np.stack([k["x"], k["y"]], 1), np.float32)
+                self.mvIniMatches = np.full(len(k), -1, np.int32)
+                self.mState = INITIALIZING
+            return self.mState, None, dict(status=None)
+        t0 = time.perf_counter()
+        k1, d1 = self.mInitialFrame
+        n1, n2 = len(k1), len(k)
+        c2 = max(n2, 1)
+        dev = "cuda"
+
+        def up(a, shape, dt):
+            buf = np.zeros(shape, dt)
+            a = np.ascontiguousarray(a, dt).reshape(-1)
+            buf.reshape(-1)[:a.size] = a
+            return torch.from_numpy(buf).to(dev)
+
+        tens = (up(k1.view(np.uint8), (1, n1, 28), np.uint8), up(d1, (1, n1, 32), np.uint8),
+                torch.tensor([n1], dtype=torch.int32, device=dev), up(k.view(np.uint8), (1, c2, 28), np.uint8),
+                up(d, (1, c2, 32), np.uint8), torch.tensor([n2], dtype=torch.int32, device=dev))
+        prev = torch.from_numpy(self.mvbPrevMatched.reshape(1, n1, 2)).to(dev)
+        rs = torch.from_numpy(self.rng_state.view(np.uint8).reshape(1, -1).copy()).to(dev)
+        t1 = time.perf_counter()
+        a = search_gate_initialize_device(self.info, self.K, *tens, prev, rs, self.thres, ctx=self.ctx)
+        status = int(a["status"].cpu()[0])
+        t2 = time.perf_counter()
+        self.mvbPrevMatched = prev.cpu().numpy().reshape(n1, 2)
+        self.mvIniMatches = a["matches12"].cpu().numpy().reshape(n1).copy()
+        self.rng_state.view(np.uint8).reshape(-1)[:] = rs.cpu().numpy().reshape(-1)
+        rep = dict(status=status, nmatches=int(a["nmatches"].cpu()[0]))
+        self.times = dict(upload=t1 - t0, search_gate_initialize=t2 - t1)
+        if status != GF_SI_OK:
+            self.mState = NOT_INITIALIZED
+            return self.mState, None, rep
+        init = a["init"].cpu().numpy().reshape(-1).view(INIT_RESULT_DTYPE).copy()
+        rep["init"] = init
+        if not int(init["ok"][0]):
+            return self.mState, None, rep
+        p3d = a["p3d"].cpu().numpy().reshape(n1, 3)
+        tri = a["triangulated"].cpu().numpy().reshape(n1)
+        t3 = time.perf_counter()
+        m, irep = create_initial_map(self.info, self.K, k1, d1, k, d, self.mvIniMatches, init, p3d, tri, voc=self.voc,
+                                     ctx=self.ctx, thres=self.thres, levelsup=self.levelsup)
+        self.mvIniMatches[(self.mvIniMatches >= 0) & (tri == 0)] = -1  # Tracking.cc:1025-1032
+        self.times.update(download=t3 - t2, create_initial_map=time.perf_counter() - t3, **{
+            "map_" + k_: v for k_, v in irep["times"].items()})
+        irep.update(rep, im_status=irep["status"], status=status)
+        self.mState = WORKING if irep["im_status"] == GF_IM_OK else NOT_INITIALIZED
+        return self.mState, m, irep

@@ -1605,6 +1605,63 @@ int gf_initial_map_finish_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, c
                               int thres_init_mpt_num,
                               gf_initmap_report* d_report, gf_map_point* d_mps, void* stream);
 
+/* ------------------------------------------------ the matches of the initialiser
+ * ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12,
+ * windowSize) (src/ORBmatcher.cc:1172-1287) over Frame::GetFeaturesInArea
+ * (src/Frame.cc:300-365) and the grid of Frame.cc:100-131, :367-377, as
+ * Tracking::Initialize calls it (src/Tracking.cc:1007-1008: ORBmatcher(0.9,
+ * true), window SRH_WINDOW_SIZE_INIT = 100). Frame 1 is the initial frame,
+ * frame 2 the current one; keypoints are the undistorted ones, octaves >= 0.
+ * Only the level-0 keypoints of both frames take part. prev_matched [n1][2]
+ * is vbPrevMatched: the window of query i is centred on prev_matched[i], and
+ * at the end every surviving match writes its frame-2 position there; other
+ * entries keep their value. matches12 [n1]: the frame-2 keypoint of query i
+ * or -1; nmatches: the reference's return value. Accept: best distance <= 50
+ * (TH_LOW) and best < (float)second * nnratio, first candidate in walk order
+ * on ties; a later accept of the same frame-2 keypoint steals it; with
+ * check_ori the rotation histogram counts every accept, also of queries robbed
+ * later (ComputeThreeMaxima, :2338-2379).
+ * flags: GF_SI_DIRECT makes every query walk its window inside the ordered
+ * pass with the distances computed in place, instead of reading the candidate
+ * list that a parallel pass stored; a query with more than 64 level-0
+ * candidates in its window does that in either mode. Same results. */
+enum { GF_SI_DIRECT = 1 };
+/* Host family: uploads, runs the device path, downloads. */
+int gf_search_for_initialization(gf_ctx* ctx, const gf_frame_info* fi, const gf_keypoint* kps1, const uint8_t* desc1,
+                                 int n1, const gf_keypoint* kps2, const uint8_t* desc2, int n2, int window,
+                                 float nnratio, int check_ori, int flags, float* prev_matched, int32_t* matches12,
+                                 int* nmatches);
+/* Device batch, laid out as gf_initialize_batch_dev lays its problems out:
+ * problem p's frames at [p][cap1] / [p][cap2] (descriptor rows 32 bytes,
+ * 16-byte aligned), d_n1[p] / d_n2[p] valid (clamped to the caps, 1 <= cap <=
+ * 4096), d_prev_matched [P][cap1][2] in / out, d_matches12 [P][cap1] (-1 past
+ * n1), d_nmatches [P]. Asynchronous on stream; the grid and the candidate
+ * lists (256 bytes per frame-1 row) live in the context's scratch. */
+int gf_search_for_initialization_batch_dev(gf_ctx* ctx, const gf_frame_info* fi, int nprob, const gf_keypoint* d_kps1,
+                                           const uint8_t* d_desc1, int cap1, const int32_t* d_n1,
+                                           const gf_keypoint* d_kps2, const uint8_t* d_desc2, int cap2,
+                                           const int32_t* d_n2, int window, float nnratio, int check_ori, int flags,
+                                           float* d_prev_matched, int32_t* d_matches12, int32_t* d_nmatches,
+                                           void* stream);
+/* The gate of Tracking::Initialize (src/Tracking.cc:999-1017) per problem,
+ * after the matcher has run on every problem of the batch. thres is
+ * THRES_INIT_MPT_NUM (100 in the reference).
+ *   GF_SI_FEW_KEYPOINTS  d_n2[p] <= thres: the reference returns before the
+ *     matcher, so d_matches12[p] becomes all -1 (:1001), d_prev_matched[p] is
+ *     restored from d_prev_before[p] (the caller's copy from before the
+ *     matcher) and d_nmatches[p] = 0; the tracker goes to NOT_INITIALIZED;
+ *   GF_SI_FEW_MATCHES    d_nmatches[p] < thres: d_matches12 and
+ *     d_prev_matched stay as the matcher left them; NOT_INITIALIZED;
+ *   GF_SI_OK             the initialiser runs.
+ * d_init_matches12 [P][cap1] is what the initialiser is to see: a copy of
+ * d_matches12 on GF_SI_OK, all -1 otherwise, so that gf_initialize_batch_dev
+ * reports ok == 0 for that problem and leaves its rand() state untouched, as
+ * the reference does not call Initializer::Initialize there. */
+enum { GF_SI_OK = 0, GF_SI_FEW_KEYPOINTS = 1, GF_SI_FEW_MATCHES = 2 };
+int gf_tracking_initialize_gate_dev(gf_ctx* ctx, int nprob, const int32_t* d_n2, int cap1, int thres,
+                                    const float* d_prev_before, float* d_prev_matched, int32_t* d_matches12,
+                                    int32_t* d_nmatches, int32_t* d_status, int32_t* d_init_matches12, void* stream);
+
 /* ------------------------------------------------ tracking glue (device)
  * Per-frame bookkeeping of Tracking between the stages above, so a front-end
  * step stays on the device. One workgroup per frame.

@@ -4,7 +4,7 @@
  * method names and argument meaning (namespace ORB_SLAM):
  *   ORBextractor            include/ORBextractor.h:47-70
  *   ORBmatcher              include/ORBmatcher.h:40-290 (M2, M3, OnePoint, Budget, SearchByBoW x2,
- *                           distance)
+ *                           SearchForInitialization, distance)
  *   Frame / KeyFrame /      include/Frame.h, include/KeyFrame.h, include/MapPoint.h (the fields
  *   MapPoint                the path reads/writes)
  *   ORBVocabulary           Thirdparty/DBoW2 TemplatedVocabulary (loaders, transform)
@@ -252,6 +252,12 @@ public:
     /* SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (:1289-1424):
      * vpMatches12[i] = pKF2's map point matched to pKF1's feature i. */
     int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12);
+    /* SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+     * (ORBmatcher.cc:1172-1287): the level-0 matches of the monocular
+     * initialiser. vnMatches12 is resized to F1's keypoints; vbPrevMatched
+     * (one entry per keypoint of F1) is updated for the surviving matches. */
+    int SearchForInitialization(Frame& F1, Frame& F2, std::vector<Point2f>& vbPrevMatched,
+                                std::vector<int>& vnMatches12, int windowSize = 10);
 
     float mfNNratio;
     bool mbCheckOrientation;
