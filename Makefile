@@ -153,6 +153,15 @@ all: $(SEARCHINITREF)
 $(SEARCHINITREF): tests/helpers/searchinit_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of Tracking::NeedNewKeyFrame / CreateNewKeyFrame,
+# KeyFrame::TrackedMapPoints, the KeyFrame snapshot and the hand-over to
+# LocalMapping (tests/test_newkeyframe_cpu.py, tests/test_newkeyframe_gpu.py),
+# same flags
+NEWKFREF = tests/helpers/libnewkeyframeref.so
+all: $(NEWKFREF)
+$(NEWKFREF): tests/helpers/newkeyframe_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

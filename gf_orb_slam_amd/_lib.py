@@ -250,6 +250,13 @@ _PROTOS = {
     "gf_frontend_read": [_P, _I, _P, _S],
     "gf_frontend_write": [_P, _I, _P, _S],
     "gf_frontend_field": [_P, _I, _P, _P],
+    "gf_need_new_keyframe": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "gf_need_new_keyframe_dev": [_P, _P, _P],
+    "gf_frontend_set_keyframes": [_P, _I, _I, _I],
+    "gf_frontend_keyframe_state_read": [_P, _P, _S],
+    "gf_frontend_keyframe_state_write": [_P, _P, _S],
+    "gf_frontend_take_keyframes": [_P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gf_frontend_keyframes_dev": [_P, _P, _P, _P, _P, _P],
     "gf_set_budgets": [_P, _D, _D],
     "gf_frontend_set_test_clock": [_P, _P],
     "gf_frontend_set_time_log": [_P, _I],

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "newkeyframe.h"
 #include "reloc.h"
 #include "undist.h"
 
@@ -906,6 +907,11 @@ struct gf_frontend {
     int tl_first = 0;            // step counter when the log was switched on
     std::vector<std::vector<int32_t>> h_slots;  // per stream: the graph's slots per keyframe
     void* bow_tmp = nullptr;
+    // NeedNewKeyFrame / CreateNewKeyFrame (gf_frontend_set_keyframes): the stage's
+    // arguments (state, outbox) in a struct of their own, and the pack buffer
+    bool kf_alloc = false, kf_on = false;
+    gf_newkf_args KA{};
+    gf::KeyframePack KP{};
 };
 
 namespace {
@@ -1160,6 +1166,9 @@ int fe_track_frame(gf_frontend* fe, hipStream_t s) {
         GF_LAUNCH(k_fe_scatter, dim3(1 + (M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK, B), 256, 0, s, D, fe->gm, WM);
         GF_HIP(hipGetLastError());
     }
+    // if(NeedNewKeyFrame()) CreateNewKeyFrame(); (Tracking.cc:896-897): after the
+    // matches are map indices again, before k_fe_end sets the outliers NULL
+    if (fe->kf_on) FE_RC(gf::need_keyframe_launch(ctx, fe->KA, s));
     {
         GF_PROF(ctx, s, "k_fe_end");
         GF_LAUNCH(k_fe_end, B, 256, 0, s, D);
@@ -1994,6 +2003,137 @@ int gf_frontend_write(gf_frontend* fe, int field, const void* host, size_t bytes
             for (int c = 0; c < 3; c++) pos[3 * i + c] = m[i].pos[c];
         GF_HIP(hipMemcpy((float*)fe->gm.pos, pos.data(), 12 * n, hipMemcpyHostToDevice));
     }
+    return GF_OK;
+}
+
+int gf_frontend_set_keyframes(gf_frontend* fe, int on, int min_frames, int max_frames) {
+    GF_CHECK(fe, GF_ERR_ARG, "null front end");
+    GF_CHECK(!fe->exec, GF_ERR_ARG, "set the keyframe stage before capturing a graph");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    if (!on) {
+        fe->kf_on = false;
+        return GF_OK;
+    }
+    GF_CHECK(min_frames >= 0, GF_ERR_ARG, "min_frames < 0");
+    GF_CHECK(fe->covis_set, GF_ERR_ARG, "the keyframe stage needs keyframe graphs (gf_frontend_set_covis)");
+    FE_RC(fe_check_covis(fe));
+    FeDev& D = fe->D;
+    const size_t B = D.B, cap = D.cap;
+    gf_newkf_args& A = fe->KA;
+    gf::KeyframePack& P = fe->KP;
+    if (!fe->kf_alloc) {
+        int rc;
+        void* p;
+#define A_(bytes, dst)                                 \
+    if ((rc = fe_alloc(fe, (bytes), &p))) return rc; \
+    dst = (decltype(dst))p;
+        A_(4 * B * GF_KF_N, A.state);
+        A_(sizeof(gf_keyframe_hdr) * B, A.out_hdr);
+        A_(sizeof(gf_keypoint) * B * cap, A.out_kps);
+        A_(32 * B * cap, A.out_desc);
+        A_(4 * B * cap, A.out_slots);
+        A_(8, P.totals);
+        A_(4 * B, P.list);
+        A_(4 * B, P.rowoff);
+        A_(sizeof(gf_keyframe_hdr) * B, P.hdr);
+        A_(sizeof(gf_keypoint) * B * cap, P.kps);
+        A_(32 * B * cap, P.desc);
+        A_(4 * B * cap, P.slots);
+#undef A_
+        fe->kf_alloc = true;
+    }
+    A.B = D.B;
+    A.cap = D.cap;
+    A.nkp = D.nkp;
+    A.kps = D.kps;
+    A.desc = D.desc;
+    A.kp2mp = D.kp2mp;
+    A.Tcw = D.Tcw;
+    A.t_cur = D.t_cur;
+    A.track = D.track;
+    A.inliers = D.stats + (size_t)GF_ST_INL2 * B;
+    A.working = D.gate_post;
+    A.ref_kf = fe->ref_kf;  // what UpdateReference left for this frame
+    A.kf_count = fe->d_kfc;
+    A.kf_mp_off = fe->cv_kf_mp_off;
+    A.kf_mp = fe->cv_kf_mp;
+    A.off_stride = gf_frontend::KF_CAP + 1;
+    A.slot_stride = (int64_t)fe->slot_cap;
+    A.min_frames = min_frames;
+    A.max_frames = max_frames > 0 ? max_frames : D.max_frames;
+    std::vector<int32_t> st(B * GF_KF_N, 0);
+    for (size_t b = 0; b < B; b++) {
+        st[b * GF_KF_N + GF_KF_ACCEPT] = 1;  // mbAcceptKeyFrames(true) (LocalMapping.cc:35)
+        st[b * GF_KF_N + GF_KF_NKF] = -1;
+    }
+    GF_HIP(hipMemcpy(A.state, st.data(), 4 * st.size(), hipMemcpyHostToDevice));
+    fe->kf_on = true;
+    return GF_OK;
+}
+
+int gf_frontend_keyframe_state_read(gf_frontend* fe, int32_t* state, size_t bytes) {
+    GF_CHECK(fe && state, GF_ERR_ARG, "null arg");
+    GF_CHECK(fe->kf_alloc, GF_ERR_ARG, "no keyframe stage (gf_frontend_set_keyframes)");
+    GF_CHECK(bytes == 4 * (size_t)fe->D.B * GF_KF_N, GF_ERR_ARG, "the state is [B][GF_KF_N] i32");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    GF_HIP(hipMemcpy(state, fe->KA.state, bytes, hipMemcpyDeviceToHost));
+    return GF_OK;
+}
+
+int gf_frontend_keyframe_state_write(gf_frontend* fe, const int32_t* state, size_t bytes) {
+    GF_CHECK(fe && state, GF_ERR_ARG, "null arg");
+    GF_CHECK(fe->kf_alloc, GF_ERR_ARG, "no keyframe stage (gf_frontend_set_keyframes)");
+    GF_CHECK(bytes == 4 * (size_t)fe->D.B * GF_KF_N, GF_ERR_ARG, "the state is [B][GF_KF_N] i32");
+    for (int b = 0; b < fe->D.B; b++)
+        GF_CHECK(!(state[(size_t)b * GF_KF_N + GF_KF_ACCEPT] && state[(size_t)b * GF_KF_N + GF_KF_PENDING]), GF_ERR_ARG,
+                 "stream " + std::to_string(b) + ": ACCEPT while its keyframe is pending (take it first)");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    GF_HIP(hipMemcpy(fe->KA.state, state, bytes, hipMemcpyHostToDevice));
+    return GF_OK;
+}
+
+int gf_frontend_take_keyframes(gf_frontend* fe, int max_kf, int rows_cap, gf_keyframe_hdr* hdr, gf_keypoint* kps,
+                               uint8_t* desc, int32_t* slots, int* nkf, int* nrows) {
+    GF_CHECK(fe && nkf && nrows, GF_ERR_ARG, "null arg");
+    GF_CHECK(fe->kf_alloc, GF_ERR_ARG, "no keyframe stage (gf_frontend_set_keyframes)");
+    GF_CHECK(max_kf >= 0 && rows_cap >= 0, GF_ERR_ARG, "negative capacity");
+    GF_CHECK(max_kf == 0 || hdr, GF_ERR_ARG, "null header array");
+    GF_CHECK(rows_cap == 0 || (kps && desc && slots), GF_ERR_ARG, "null row arrays");
+    *nkf = *nrows = 0;
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    hipStream_t s = fe->ctx->stream;
+    const gf::KeyframePack& P = fe->KP;
+    FE_RC(gf::keyframe_pack_launch(fe->ctx, fe->KA, P, std::min(max_kf, fe->D.B), s));
+    int32_t tot[2] = {0, 0};
+    GF_HIP(hipMemcpyAsync(tot, P.totals, 8, hipMemcpyDeviceToHost, s));
+    GF_HIP(hipStreamSynchronize(s));
+    *nrows = tot[1];
+    GF_CHECK(tot[1] <= rows_cap, GF_ERR_CAP, "the pending keyframes hold " + std::to_string(tot[1]) + " rows");
+    const size_t k = tot[0], r = tot[1];
+    if (k) GF_HIP(hipMemcpyAsync(hdr, P.hdr, sizeof(gf_keyframe_hdr) * k, hipMemcpyDeviceToHost, s));
+    if (r) {
+        GF_HIP(hipMemcpyAsync(kps, P.kps, sizeof(gf_keypoint) * r, hipMemcpyDeviceToHost, s));
+        GF_HIP(hipMemcpyAsync(desc, P.desc, 32 * r, hipMemcpyDeviceToHost, s));
+        GF_HIP(hipMemcpyAsync(slots, P.slots, 4 * r, hipMemcpyDeviceToHost, s));
+    }
+    if (k) FE_RC(gf::keyframe_clear_launch(fe->ctx, fe->KA, P, s));
+    GF_HIP(hipStreamSynchronize(s));
+    *nkf = tot[0];
+    return GF_OK;
+}
+
+int gf_frontend_keyframes_dev(gf_frontend* fe, int32_t** d_state, gf_keyframe_hdr** d_hdr, gf_keypoint** d_kps,
+                              uint8_t** d_desc, int32_t** d_slots) {
+    GF_CHECK(fe, GF_ERR_ARG, "null front end");
+    GF_CHECK(fe->kf_alloc, GF_ERR_ARG, "no keyframe stage (gf_frontend_set_keyframes)");
+    if (d_state) *d_state = fe->KA.state;
+    if (d_hdr) *d_hdr = fe->KA.out_hdr;
+    if (d_kps) *d_kps = fe->KA.out_kps;
+    if (d_desc) *d_desc = fe->KA.out_desc;
+    if (d_slots) *d_slots = fe->KA.out_slots;
     return GF_OK;
 }
 

@@ -79,6 +79,37 @@ PATHS = {0: "motion model", 1: "previous frame after the motion model", 2: "prev
 
 NSTAT = len(STATS)
 
+# NeedNewKeyFrame / CreateNewKeyFrame state words (abi.h GF_KF_*) and decision bits
+KF = {"since": 0, "accept": 1, "stop": 2, "nkf": 3, "abort": 4, "decision": 5, "ref": 6, "ref_matches": 7,
+      "inliers": 8, "seq": 9, "pending": 10, "frame": 11}
+KF_N = 16
+KF_BITS = {"evaluated": 1, "stop": 2, "reloc": 4, "c1a": 8, "c1b": 16, "c2": 32, "created": 64, "interrupt_ba": 128,
+           "no_reference": 256}
+KEYFRAME_HDR_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("frame_id", "<i4"), ("n", "<i4"),
+                               ("timestamp", "<f8"), ("Tcw", "<f4", (16,))])  # gf_keyframe_hdr
+assert KEYFRAME_HDR_DTYPE.itemsize == 88
+
+
+class NewKfArgs(ctypes.Structure):
+    """gf_newkf_args (device pointers)."""
+
+    _fields_ = ([("B", ctypes.c_int32), ("cap", ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in ("nkp", "kps", "desc", "kp2mp", "Tcw", "t_cur", "track", "inliers",
+                                                "working", "ref_kf", "kf_count", "kf_mp_off", "kf_mp")] +
+                [("off_stride", ctypes.c_int64), ("slot_stride", ctypes.c_int64)] +
+                [(k, ctypes.c_void_p) for k in ("state", "out_hdr", "out_kps", "out_desc", "out_slots")] +
+                [("min_frames", ctypes.c_int32), ("max_frames", ctypes.c_int32)])
+
+
+def need_new_keyframe(since_kf: int, since_reloc: int, stop: bool, nkf: int, n_ref_matches: int, inliers: int,
+                      accept: bool, min_frames: int, max_frames: int):
+    """gf_need_new_keyframe: Tracking::NeedNewKeyFrame on scalars -> (need, GF_KF_DECISION bits)."""
+    need, dec = ctypes.c_int(), ctypes.c_int()
+    check(lib().gf_need_new_keyframe(int(since_kf), int(since_reloc), int(bool(stop)), int(nkf), int(n_ref_matches),
+                                     int(inliers), int(bool(accept)), int(min_frames), int(max_frames),
+                                     ctypes.byref(need), ctypes.byref(dec)))
+    return bool(need.value), dec.value
+
 # per-frame stage log (abi.h GF_TL_*, gf_time_rec): device-clock boundaries of a step
 TL_SITES = ["begin", "extracted", "motion", "init_pose", "ref_updated", "frustum", "mat_online", "selected",
             "searched", "optimised", "end"]
@@ -439,6 +470,65 @@ class FrontEnd:
     def stats(self) -> dict:
         s = self.read("stats")
         return {k: s[i] for i, k in enumerate(STATS)}
+
+    # ------------------------------------------------------------ keyframes
+    def enable_keyframes(self, min_frames: int = 0, max_frames: int | None = None, on: bool = True) -> None:
+        """gf_frontend_set_keyframes: `if(NeedNewKeyFrame()) CreateNewKeyFrame();`
+        (Tracking.cc:896-897) as a stage of every following step. min_frames =
+        mMinFrames (0, :151), max_frames None = the front end's mMaxFrames.
+        Needs a keyframe graph on every stream; before capture_graph()."""
+        check(lib().gf_frontend_set_keyframes(self.handle, int(on), int(min_frames), int(max_frames or 0)))
+
+    def keyframe_state(self) -> dict:
+        """The GF_KF_* words: {name: [B] i32} over KF."""
+        st = np.zeros((self.B, KF_N), np.int32)
+        check(lib().gf_frontend_keyframe_state_read(self.handle, ptr(st), st.nbytes))
+        return {k: st[:, i].copy() for k, i in KF.items()}
+
+    def set_keyframe_state(self, stream: int | None = None, **words) -> None:
+        """Write state words (names of KF) on one stream or, stream None, on all
+        (a scalar or a [B] array each); the others keep their values. ACCEPT on
+        a stream whose keyframe is pending is refused."""
+        bad = set(words) - set(KF)
+        if bad:
+            raise ValueError(f"unknown keyframe state words {sorted(bad)}")
+        st = np.zeros((self.B, KF_N), np.int32)
+        check(lib().gf_frontend_keyframe_state_read(self.handle, ptr(st), st.nbytes))
+        for k, v in words.items():
+            if stream is None:
+                st[:, KF[k]] = np.asarray(v, np.int32)
+            else:
+                st[stream, KF[k]] = int(v)
+        check(lib().gf_frontend_keyframe_state_write(self.handle, ptr(st), st.nbytes))
+
+    def take_keyframes(self, max_kf: int | None = None) -> list:
+        """gf_frontend_take_keyframes: the pending keyframes (lowest streams
+        first, at most max_kf), their PENDING cleared -> a list of
+        dict(stream, seq, frame_id, timestamp, Tcw [4][4], kps, desc, slots);
+        slots are map indices with the outliers still in place."""
+        k = self.B if max_kf is None else max(0, min(int(max_kf), self.B))
+        rows = k * self.cap
+        hdr = np.zeros(max(k, 1), KEYFRAME_HDR_DTYPE)
+        kps = np.zeros(max(rows, 1), KEYPOINT_DTYPE)
+        desc = np.zeros((max(rows, 1), 32), np.uint8)
+        slots = np.zeros(max(rows, 1), np.int32)
+        nkf, nrows = ctypes.c_int(), ctypes.c_int()
+        check(lib().gf_frontend_take_keyframes(self.handle, k, rows, ptr(hdr), ptr(kps), ptr(desc), ptr(slots),
+                                               ctypes.byref(nkf), ctypes.byref(nrows)))
+        out, r = [], 0
+        for h in hdr[:nkf.value]:
+            n = int(h["n"])
+            out.append(dict(stream=int(h["stream"]), seq=int(h["seq"]), frame_id=int(h["frame_id"]),
+                            timestamp=float(h["timestamp"]), Tcw=h["Tcw"].reshape(4, 4).copy(),
+                            kps=kps[r:r + n].copy(), desc=desc[r:r + n].copy(), slots=slots[r:r + n].copy()))
+            r += n
+        return out
+
+    def keyframes_dev(self) -> dict:
+        """gf_frontend_keyframes_dev: device addresses of the state and the outbox."""
+        p = [ctypes.c_void_p() for _ in range(5)]
+        check(lib().gf_frontend_keyframes_dev(self.handle, *[ctypes.byref(x) for x in p]))
+        return dict(zip(("state", "hdr", "kps", "desc", "slots"), (x.value for x in p)))
 
     # ------------------------------------------------------------ profiling
     def prof_enable(self, on: bool = True) -> None:

@@ -448,3 +448,105 @@ class MonoInitializer:
         irep.update(rep, im_status=irep["status"], status=status)
         self.mState = WORKING if irep["im_status"] == GF_IM_OK else NOT_INITIALIZED
         return self.mState, m, irep
+
+
+# ------------------------------------------------ NeedNewKeyFrame / CreateNewKeyFrame -> LocalMapping
+def loopmap_from_global_map(info, gm, voc=None, ctx=None, levelsup: int = 4):
+    """A ``LoopMap`` over a ``scene.build_global_map`` entry ``gm``, the map a
+    front-end stream tracks (``FrontEnd.set_map`` / ``set_covis`` of the same
+    entry): point id = map index, keyframe index = graph index, the slot
+    tables from the graph's CSR, the poses ``gm["kf_Tcw"]``. With ``voc``
+    every keyframe gets its ``ComputeBoW`` (what CreateNewMapPoints reads of
+    the neighbours); the covisibility graph is ``UpdateConnections`` of every
+    keyframe, in index order."""
+    from .bow import FeatureVector
+    from .loopmap import LoopMap
+
+    g = gm["graph"]
+    off = np.asarray(g["kf_mp_off"], np.int64)
+    kf_mp = [np.asarray(g["kf_mp"][off[k]:off[k + 1]], np.int32) for k in range(len(off) - 1)]
+    m = LoopMap(info, gm["kf_kps"], gm["kf_desc"], kf_mp, gm["mp"], gm["desc"], mp_bad=g["mp_bad"], kf_bad=g["kf_bad"],
+                kf_Tcw=np.asarray(gm["kf_Tcw"], np.float32))
+    if voc is not None:
+        transform = voc.transform if hasattr(voc, "transform") else voc
+        for k in range(m.nkf):
+            words, values, fv = transform(m.kf_desc[k], levelsup)
+            m.kf_bow[k] = (words, values)
+            m.kf_fv[k] = fv if isinstance(fv, FeatureVector) else FeatureVector(*fv)
+    m.update_connections_batch(range(m.nkf), ctx)
+    return m
+
+
+class KeyFrameInserter:
+    """The half of ``LocalMapping``'s interface that faces tracking, without
+    the thread: ``InsertKeyFrame`` (LocalMapping.cc:149-155), the queue
+    ``mlNewKeyFrames`` with ``CheckNewKeyFrames`` (:158-162), ``SetAcceptKeyFrames``
+    (:70, :116-117), ``mbAbortBA`` (:98, :100, :153) and ``RequestStop`` /
+    ``Release`` (:132-141), between a ``pipeline.FrontEnd`` whose keyframe stage
+    is on and one ``LocalMapper`` per stream (a dict or a list; a stream
+    without a mapper is left alone).
+
+    point_ids[stream] (optional) maps the front end's map index to the
+    mapper's point id (identity by default; -1 stays -1)."""
+
+    def __init__(self, fe, mappers, point_ids=None):
+        self.fe = fe
+        self.mappers = dict(mappers) if isinstance(mappers, dict) else dict(enumerate(mappers))
+        self.point_ids = dict(point_ids or {})
+        self.queue = {b: [] for b in self.mappers}       # mlNewKeyFrames: keyframe indices
+        self.stop_flags = {b: ctypes.c_uint8(0) for b in self.mappers}  # the byte LocalBundleAdjustment polls
+        self.stop_requested = {b: False for b in self.mappers}
+        self.taken = []  # every keyframe handed over, in order: (stream, keyframe index, header fields)
+
+    def pump(self) -> list:
+        """Take the pending keyframes of the mapped streams' front end, insert
+        each into its stream's map and queue it; raise the stop byte of a
+        stream whose ABORT word the device set. -> [(stream, keyframe index)]."""
+        abort = self.fe.keyframe_state()["abort"]
+        for b in self.mappers:
+            if abort[b]:
+                self.stop_flags[b].value = 1  # mbAbortBA as LocalBundleAdjustment's pbStopFlag sees it
+        out = []
+        for kf in self.fe.take_keyframes():
+            b = kf["stream"]
+            if b not in self.mappers:
+                continue
+            slots = kf["slots"]
+            ids = self.point_ids.get(b)
+            if ids is not None:
+                ids = np.asarray(ids, np.int32)
+                slots = np.where(slots >= 0, ids[np.maximum(slots, 0)], -1).astype(np.int32)
+            k = self.mappers[b].insert_keyframe(kf["kps"], kf["desc"], slots, kf["Tcw"])
+            self.queue[b].append(k)
+            self.taken.append((b, k, {x: kf[x] for x in ("seq", "frame_id", "timestamp")}))
+            out.append((b, k))
+        return out
+
+    def run_mapper(self, stream: int):
+        """One pass of LocalMapping::Run's body (:58-124) for the stream's
+        oldest queued keyframe -> the ``LocalMapper.step`` report, or None with
+        an empty queue. mbAbortBA is cleared first (:98); local BA is skipped
+        when more keyframes wait or a stop was requested (:100); ACCEPT comes
+        back when the queue is empty (:116-117)."""
+        q = self.queue[stream]
+        if not q:
+            return None
+        cur = q.pop(0)
+        self.fe.set_keyframe_state(stream, abort=0)
+        self.stop_flags[stream].value = 0
+        abort_ba = bool(q) or self.stop_requested[stream]
+        rep = self.mappers[stream].step(cur, abort_ba=abort_ba, stop_flag=self.stop_flags[stream])
+        if not q:
+            self.fe.set_keyframe_state(stream, accept=1)
+        return rep
+
+    def request_stop(self, stream: int) -> None:
+        """LocalMapping::RequestStop (:132-135): the stream inserts no keyframe
+        (Tracking.cc:3042) and its next mapper pass skips local BA."""
+        self.stop_requested[stream] = True
+        self.fe.set_keyframe_state(stream, stop=1)
+
+    def release(self, stream: int) -> None:
+        """LocalMapping::Release (:138-141)."""
+        self.stop_requested[stream] = False
+        self.fe.set_keyframe_state(stream, stop=0)

@@ -1706,8 +1706,11 @@ int gf_views_exclude_matched_dev(gf_ctx* ctx, int nframes, const int32_t* d_kp2m
  *     (:3097-3145: isInFrustum when mbNeedVizCheck, SearchByProjection_Budget
  *     th 0.8), outliers set NULL, mLastFrame = Frame(mCurrentFrame) (:901-910).
  * The local map (UpdateReference, :3689-3852) is the map set with
- * gf_frontend_set_map, in that order; keyframe insertion and local mapping
- * are outside the path. The tracking state machine of GrabImage
+ * gf_frontend_set_map, in that order. Keyframe insertion
+ * (NeedNewKeyFrame / CreateNewKeyFrame, :896-897) is a stage of the step once
+ * gf_frontend_set_keyframes switched it on; local mapping takes the keyframes
+ * from its outbox (gf_frontend_take_keyframes) and runs outside the path. The
+ * tracking state machine of GrabImage
  * (:602-644, 652-716, 854-911) runs per stream (GF_FE_TRACK):
  *   WORKING with a velocity and >= 2 frames since a relocalisation:
  *     TrackWithMotionModel; it fails on < 20 matches (:1559) or < 10 after
@@ -2021,6 +2024,119 @@ int gf_frontend_read(gf_frontend* fe, int field, void* host, size_t bytes);
 int gf_frontend_write(gf_frontend* fe, int field, const void* host, size_t bytes);
 /* Size and device pointer of a field. */
 int gf_frontend_field(gf_frontend* fe, int field, size_t* bytes, void** d_ptr);
+
+/* ------------------------------------- NeedNewKeyFrame / CreateNewKeyFrame
+ * `if(NeedNewKeyFrame()) CreateNewKeyFrame();` (Tracking.cc:896-897), the
+ * only way a frame becomes a keyframe: a stage of the step between the
+ * hand-back of the local map and the NULLing of the outlier matches
+ * (:899-907), so the keyframe carries the outliers and bundle adjustment
+ * decides about them (:899-902). Off until gf_frontend_set_keyframes.
+ * Per-stream state, [B][GF_KF_N] i32 (not a GF_FE_* field; read and written
+ * with gf_frontend_keyframe_state_read / _write):                          */
+enum {
+    GF_KF_SINCE = 0,    /* mnId - mnLastKeyFrameId: + 1 every step for every stream
+                           (saturates at 1 << 30), 0 on creation and when the stage
+                           is enabled (Tracking.cc:1309); host-writable              */
+    GF_KF_ACCEPT,       /* mbAcceptKeyFrames (LocalMapping.cc:566-576): set by the
+                           host, cleared on creation (:70)                           */
+    GF_KF_STOP,         /* isStopped() || stopRequested() (:3042); host only         */
+    GF_KF_NKF,          /* KeyFramesInMap() (:3046); -1: the keyframe graph's count  */
+    GF_KF_ABORT,        /* mbAbortBA: raised on creation (LocalMapping.cc:153) and by
+                           InterruptBA (:3071); cleared by the host (LocalMapping.cc:98) */
+    GF_KF_DECISION,     /* bits of the last step: 1 evaluated (the frame ended
+                           WORKING), 2 refused by the stop test (:3042), 4 refused by
+                           the relocalisation test (:3046), 8 c1a, 16 c1b, 32 c2,
+                           64 created, 128 InterruptBA, 256 no reference keyframe
+                           (verdict false; the reference would dereference NULL,
+                           :3050 after :3851). Tests not reached leave their bits 0 */
+    GF_KF_REF,          /* mpReferenceKF (keyframe index) the rule read; -1 when
+                           not evaluated or none                                     */
+    GF_KF_REF_MATCHES,  /* nRefMatches = mpReferenceKF->TrackedMapPoints()
+                           (KeyFrame.cc:253-265); 0 when not evaluated / no reference */
+    GF_KF_INLIERS,      /* mnMatchesInliers the rule read; 0 when not evaluated      */
+    GF_KF_SEQ,          /* keyframes created so far                                  */
+    GF_KF_PENDING,      /* 1: the outbox slot holds a keyframe not yet taken         */
+    GF_KF_FRAME,        /* its mnFrameId (GF_TR_QUERY of the creating step)          */
+    GF_KF_N = 16
+};
+/* Header of a keyframe in the outbox / of a taken keyframe: `new
+ * KeyFrame(mCurrentFrame, ...)` (KeyFrame.cc:30-54) without the rows. */
+typedef struct gf_keyframe_hdr {
+    int32_t stream, seq;        /* the creating stream, its GF_KF_SEQ after creation */
+    int32_t frame_id, n;        /* mnFrameId, N                                      */
+    double timestamp;           /* mTimeStamp                                        */
+    float Tcw[16];              /* mTcw                                              */
+} gf_keyframe_hdr;
+/* Tracking::NeedNewKeyFrame (Tracking.cc:3035-3077) alone, host, scalar, in
+ * the reference's order and arithmetic (c2's product is a double). since_kf =
+ * mnId - mnLastKeyFrameId, since_reloc = mnId - mnLastRelocFrameId, stop =
+ * isStopped() || stopRequested(), nkf = KeyFramesInMap(), n_ref_matches =
+ * mpReferenceKF->TrackedMapPoints() (< 0: no reference keyframe), accept =
+ * AcceptKeyFrames(). *decision (optional) gets the GF_KF_DECISION bits with 1
+ * set; *need 1 / 0; InterruptBA is bit 128 (the caller raises mbAbortBA). */
+int gf_need_new_keyframe(int since_kf, int since_reloc, int stop, int nkf, int n_ref_matches, int inliers, int accept,
+                         int min_frames, int max_frames, int* need, int* decision);
+/* The stage on explicit device arrays (the step launches the same kernel, one
+ * workgroup per stream): the rule of :3035-3077 with nRefMatches counted from
+ * the reference keyframe's slot row, the state words updated as listed at
+ * GF_KF_*, and for a stream that creates the snapshot of KeyFrame.cc:30-54
+ * into its outbox slot with the effects of CreateNewKeyFrame (:3079-3092) and
+ * LocalMapping::InsertKeyFrame (LocalMapping.cc:149-155). A stream that does
+ * not create writes nothing into the outbox; no stream writes a row >= N. */
+typedef struct gf_newkf_args {
+    int32_t B, cap;             /* streams, keypoint rows per stream                 */
+    const int32_t* nkp;         /* [B] N                                             */
+    const gf_keypoint* kps;     /* [B][cap] mvKeysUn                                 */
+    const uint8_t* desc;        /* [B][cap][32] mDescriptors                         */
+    const int32_t* kp2mp;       /* [B][cap] mvpMapPoints (map index, -1 NULL)        */
+    const float* Tcw;           /* [B][16] mTcw                                      */
+    const double* t_cur;        /* [B] mTimeStamp                                    */
+    const int32_t* track;       /* [B][GF_TR_N]: GF_TR_SINCE, GF_TR_QUERY are read   */
+    const int32_t* inliers;     /* [B] mnMatchesInliers                              */
+    const int32_t* working;     /* [B] != 0: the frame ended WORKING (:854)          */
+    const int32_t* ref_kf;      /* [B] mpReferenceKF as a keyframe index, -1 none    */
+    const int32_t* kf_count;    /* [B] keyframes of the stream's graph               */
+    const int32_t* kf_mp_off;   /* [B][off_stride] CSR of KeyFrame::mvpMapPoints     */
+    const int32_t* kf_mp;       /* [B][slot_stride] map index per slot, -1 NULL      */
+    int64_t off_stride, slot_stride;
+    int32_t* state;             /* [B][GF_KF_N]                                      */
+    gf_keyframe_hdr* out_hdr;   /* [B]       the outbox                              */
+    gf_keypoint* out_kps;       /* [B][cap]                                          */
+    uint8_t* out_desc;          /* [B][cap][32]                                      */
+    int32_t* out_slots;         /* [B][cap]                                          */
+    int32_t min_frames;         /* mMinFrames (0, Tracking.cc:151)                   */
+    int32_t max_frames;         /* mMaxFrames (:153)                                 */
+} gf_newkf_args;
+int gf_need_new_keyframe_dev(gf_ctx* ctx, const gf_newkf_args* args, void* stream);
+/* Switch the stage on / off for the following steps: min_frames = mMinFrames
+ * (0 in the reference, Tracking.cc:151), max_frames <= 0 = the front end's
+ * mMaxFrames. Needs a keyframe graph on every stream (gf_frontend_set_covis)
+ * and comes before gf_frontend_capture, like the other set calls. Allocates
+ * the state and the outbox on first use and resets the state: SINCE 0 (as
+ * after :1309), ACCEPT 1, NKF -1, everything else 0. Off is the default, and
+ * with the stage off a step launches exactly what it launched without it. */
+int gf_frontend_set_keyframes(gf_frontend* fe, int on, int min_frames, int max_frames);
+/* The state words of every stream, [B][GF_KF_N] i32 (synchronises). The write
+ * refuses (GF_ERR_ARG, nothing written) a state with ACCEPT and PENDING both
+ * set on a stream: mbAcceptKeyFrames comes back only after the keyframe was
+ * taken (LocalMapping.cc:116-117), so the device never overwrites an untaken
+ * keyframe. */
+int gf_frontend_keyframe_state_read(gf_frontend* fe, int32_t* state, size_t bytes);
+int gf_frontend_keyframe_state_write(gf_frontend* fe, const int32_t* state, size_t bytes);
+/* mlNewKeyFrames' hand-over (LocalMapping.cc:149-155, 168-176): the pending
+ * outbox slots packed on the device into one contiguous buffer, downloaded,
+ * and their PENDING cleared. Streams ascending; at most max_kf keyframes, the
+ * lowest streams first. hdr [max_kf]; keyframe j's rows are
+ * [sum of hdr[i].n for i < j, + hdr[j].n) of kps / desc ([rows_cap][32]) /
+ * slots (map indices, outliers still in place). *nkf keyframes taken, *nrows
+ * their rows. rows_cap too small: GF_ERR_CAP, nothing taken, *nrows = need. */
+int gf_frontend_take_keyframes(gf_frontend* fe, int max_kf, int rows_cap, gf_keyframe_hdr* hdr, gf_keypoint* kps,
+                               uint8_t* desc, int32_t* slots, int* nkf, int* nrows);
+/* The device pointers of the state and the outbox ([B][GF_KF_N], [B],
+ * [B][cap], [B][cap][32], [B][cap]) for a caller that stays on the device;
+ * any may be NULL. */
+int gf_frontend_keyframes_dev(gf_frontend* fe, int32_t** d_state, gf_keyframe_hdr** d_hdr, gf_keypoint** d_kps,
+                              uint8_t** d_desc, int32_t** d_slots);
 
 /* Wall-clock budgets of the reference's time-capped loops, in seconds; +inf
  * (the default) is parity mode: no loop is cut and no clock is read.

@@ -369,6 +369,39 @@ public:
     static void BundleAdjustment(LocalBAWindow* pWindow, int nIterations, bool* pbStopFlag = nullptr);
 };
 
+/* ---------------------------------------------------------------- Tracking::NeedNewKeyFrame */
+/* What Tracking::NeedNewKeyFrame (Tracking.cc:3035-3077) reads, as values:
+ * mCurrentFrame.mnId, mnLastKeyFrameId, mnLastRelocFrameId, mMinFrames,
+ * mMaxFrames, mnMatchesInliers, mpMap->KeyFramesInMap(),
+ * mpReferenceKF->TrackedMapPoints() (< 0: no reference keyframe, the verdict
+ * is false) and the local mapper's isStopped() || stopRequested() and
+ * AcceptKeyFrames(). */
+struct KeyFrameDecisionInput {
+    long unsigned int mnId = 0, mnLastKeyFrameId = 0, mnLastRelocFrameId = 0;
+    int mMinFrames = 0, mMaxFrames = 0;
+    int mnMatchesInliers = 0;
+    int nKeyFramesInMap = 0;
+    int nRefMatches = -1;
+    bool bLocalMapperStopped = false;   /* isStopped() || stopRequested() */
+    bool bAcceptKeyFrames = true;
+};
+/* The rule over gf_need_new_keyframe. *pbInterruptBA (optional) is set when
+ * the reference would call mpLocalMapper->InterruptBA() (:3071), *pnDecision
+ * (optional) gets the GF_KF_DECISION bits. */
+inline bool NeedNewKeyFrame(const KeyFrameDecisionInput& in, bool* pbInterruptBA = nullptr,
+                            int* pnDecision = nullptr) {
+    const long unsigned int kSat = 1u << 30;
+    const long unsigned int sinceKF = in.mnId - in.mnLastKeyFrameId, sinceReloc = in.mnId - in.mnLastRelocFrameId;
+    int need = 0, decision = 0;
+    if (gf_need_new_keyframe((int)(sinceKF < kSat ? sinceKF : kSat), (int)(sinceReloc < kSat ? sinceReloc : kSat),
+                             in.bLocalMapperStopped ? 1 : 0, in.nKeyFramesInMap, in.nRefMatches, in.mnMatchesInliers,
+                             in.bAcceptKeyFrames ? 1 : 0, in.mMinFrames, in.mMaxFrames, &need, &decision) != GF_OK)
+        throw std::runtime_error("gf_need_new_keyframe failed");
+    if (pbInterruptBA) *pbInterruptBA = (decision & 128) != 0;
+    if (pnDecision) *pnDecision = decision;
+    return need != 0;
+}
+
 }  // namespace ORB_SLAM
 
 #endif /* GFSLAM_ORBSLAM_H */
