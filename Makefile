@@ -162,6 +162,14 @@ all: $(NEWKFREF)
 $(NEWKFREF): tests/helpers/newkeyframe_ref.cpp
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of gf_frontend_update_maps: a map delta's verdict
+# and the delta applied to one stream's flat arrays
+# (tests/test_mapupdate_cpu.py, tests/test_mapupdate_gpu.py), same flags
+MAPUPDATEREF = tests/helpers/libmapupdateref.so
+all: $(MAPUPDATEREF)
+$(MAPUPDATEREF): tests/helpers/mapupdate_ref.cpp include/gfslam/abi.h
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mapupdate.h"
 #include "newkeyframe.h"
 #include "reloc.h"
 #include "undist.h"
@@ -912,6 +913,19 @@ struct gf_frontend {
     bool kf_alloc = false, kf_on = false;
     gf_newkf_args KA{};
     gf::KeyframePack KP{};
+    // map feedback (gf_frontend_update_maps): host mirrors of what the graphs
+    // hold beside h_nmp / h_kfc / h_slots (h_nmp -1: read from the device on
+    // the next call), the device staging with the observation rebuild's
+    // tables, and two pinned upload buffers used in turn (an upload in flight
+    // is never overwritten: its event is waited for before the buffer's reuse)
+    std::vector<int32_t> h_nc;                    // covisibility entries
+    std::vector<std::vector<int32_t>> h_obs_len;  // observation row lengths
+    uint8_t* mu_stage = nullptr;
+    size_t mu_bytes = 0, mu_stream_bytes = 0;
+    int32_t *mu_off_new = nullptr, *mu_obs_new = nullptr;
+    uint8_t* mu_pin[2] = {nullptr, nullptr};
+    hipEvent_t mu_ev[2] = {nullptr, nullptr};
+    int mu_turn = 0;
 };
 
 namespace {
@@ -949,6 +963,12 @@ void fe_free(gf_frontend* fe) {
     fe_drop_graph(fe);
     for (void* p : fe->allocs) (void)hipFree(p);
     fe->allocs.clear();
+    for (int i = 0; i < 2; i++) {
+        if (fe->mu_pin[i]) (void)hipHostFree(fe->mu_pin[i]);
+        if (fe->mu_ev[i]) (void)hipEventDestroy(fe->mu_ev[i]);
+        fe->mu_pin[i] = nullptr;
+        fe->mu_ev[i] = nullptr;
+    }
     if (fe->ex) (void)gf_extractor_destroy(fe->ex);
     fe->ex = nullptr;
 }
@@ -1370,6 +1390,7 @@ int gf_frontend_create(gf_ctx* ctx, const gf_frontend_params* p, gf_frontend** o
     D.gupd = D.upd;
     D.refmap = 0;
     fe->has_covis.assign(B, 0);
+    fe->h_nmp.assign(B, 0);
     const uint8_t** ptrs = nullptr;
     F(-1, const uint8_t*, B, ptrs);
     D.ptrs = ptrs;
@@ -1505,6 +1526,7 @@ int gf_frontend_set_map(gf_frontend* fe, int stream, const gf_map_point* mps, co
         GF_HIP(hipMemcpy((float*)fe->gm.pos + 3 * o, pos.data(), 12 * (size_t)m, hipMemcpyHostToDevice));
     }
     GF_HIP(hipMemcpy(fe->g_nmp + stream, &m, 4, hipMemcpyHostToDevice));
+    fe->h_nmp[stream] = m;
     std::vector<int32_t> neg(M, -1000);
     GF_HIP(hipMemcpy(fe->gm.upd + o, neg.data(), 4 * M, hipMemcpyHostToDevice));
     GF_HIP(hipMemset(fe->gm.views + o, 0, sizeof(gf_mp_view) * M));
@@ -1554,6 +1576,8 @@ static int fe_enable_covis(gf_frontend* fe) {
     fe->covis_set = 1;
     fe->TL.covis = fe->d_covis;
     fe->h_slots.assign(B, {});
+    fe->h_nc.assign(B, 0);
+    fe->h_obs_len.assign(B, {});
     return GF_OK;
 }
 
@@ -1621,6 +1645,10 @@ int gf_frontend_set_covis(gf_frontend* fe, int stream, const gf_covis_map* g) {
     GF_HIP(hipMemcpy(fe->d_kfc + b, &fe->h_kfc[b], 4, hipMemcpyHostToDevice));
     fe->h_slots[b].resize(nkf);
     for (int k = 0; k < nkf; k++) fe->h_slots[b][k] = g->kf_mp_off[k + 1] - g->kf_mp_off[k];
+    fe->h_nmp[b] = nmp;
+    fe->h_nc[b] = (int32_t)nc;
+    fe->h_obs_len[b].resize(nmp);
+    for (int m = 0; m < nmp; m++) fe->h_obs_len[b][m] = g->mp_obs_off[m + 1] - g->mp_obs_off[m];
     if (fe->rl_alloc && fe->h_kfdb[b].nkf) FE_RC(gf_frontend_set_kfdb(fe, stream, nullptr));
     return GF_OK;
 }
@@ -2003,6 +2031,338 @@ int gf_frontend_write(gf_frontend* fe, int field, const void* host, size_t bytes
             for (int c = 0; c < 3; c++) pos[3 * i + c] = m[i].pos[c];
         GF_HIP(hipMemcpy((float*)fe->gm.pos, pos.data(), 12 * n, hipMemcpyHostToDevice));
     }
+    if (field == GF_FE_NMP) {  // the host mirror gf_frontend_update_maps validates against
+        const int32_t* n = (const int32_t*)host;
+        for (int b = 0; b < fe->D.B; b++) fe->h_nmp[b] = n[b];
+    }
+    return GF_OK;
+}
+
+// ---------------------------------------------------------------- map feedback
+namespace {
+
+inline size_t mu_a16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// What one delta does to its stream's sizes, and the arrays the host derives.
+struct MuPlan {
+    gf::MuHdr h{};
+    std::vector<int32_t> slot_pos, row_of, kf_off;
+};
+
+// Staging bytes one stream can need at the capacities (the sections of MuHdr).
+size_t mu_stream_cap_bytes(size_t M, size_t slot_cap, size_t KC) {
+    return sizeof(gf::MuHdr) + 16 + 2 * mu_a16(32 * M) + mu_a16(M)      // appended points
+           + mu_a16(4 * M) + 2 * mu_a16(32 * M)                         // rewritten points
+           + mu_a16(4 * M) + mu_a16(4 * KC)                             // bad lists
+           + mu_a16(4 * (KC + 1)) + mu_a16(4 * slot_cap) + mu_a16(KC)   // appended keyframes
+           + 2 * mu_a16(4 * slot_cap)                                   // slot writes
+           + mu_a16(4 * M) + mu_a16(4 * (M + 2)) + mu_a16(4 * slot_cap) // observation rows
+           + mu_a16(4 * (KC + 1)) + mu_a16(4 * KC * KC);                // covisibility
+}
+
+int mu_validate(gf_frontend* fe, const gf_map_delta& d, MuPlan& P) {
+    const int b = d.stream, M = fe->D.M, KC = gf_frontend::KF_CAP;
+    const std::string at = "stream " + std::to_string(b) + ": ";
+    GF_CHECK(fe->has_covis[b], GF_ERR_ARG, at + "no keyframe graph (gf_frontend_set_covis)");
+    GF_CHECK(d.n_new_mp >= 0 && d.n_set_mp >= 0 && d.n_bad_mp >= 0 && d.n_new_kf >= 0 && d.n_bad_kf >= 0 &&
+                 d.n_slot >= 0 && d.n_obs_rows >= 0,
+             GF_ERR_ARG, at + "negative count");
+    GF_CHECK((!d.n_new_mp || (d.new_mp && d.new_mp_desc)) && (!d.n_set_mp || (d.set_mp_idx && d.set_mp && d.set_mp_desc)) &&
+                 (!d.n_bad_mp || d.bad_mp) && (!d.n_new_kf || d.new_kf_off) && (!d.n_bad_kf || d.bad_kf) &&
+                 (!d.n_slot || (d.slot_kf && d.slot_idx && d.slot_val)) && (!d.n_obs_rows || (d.obs_mp && d.obs_off)) &&
+                 (!d.has_cov || d.kf_cov_off),
+             GF_ERR_ARG, at + "null array");
+    gf::MuHdr& h = P.h;
+    h.stream = b;
+    h.nmp0 = fe->h_nmp[b];
+    h.nkf0 = fe->h_kfc[b];
+    GF_CHECK((long long)h.nmp0 + d.n_new_mp <= M, GF_ERR_CAP, at + "more map points than map_cap");
+    GF_CHECK((long long)h.nkf0 + d.n_new_kf <= KC, GF_ERR_CAP, at + "more than 64 keyframes");
+    h.nmp1 = h.nmp0 + d.n_new_mp;
+    h.nkf1 = h.nkf0 + d.n_new_kf;
+    GF_CHECK(!(d.n_new_kf && fe->rl_alloc && fe->h_kfdb[b].nkf), GF_ERR_UNSUPPORTED,
+             at + "a keyframe database is attached: it cannot grow with the graph (detach it first)");
+    std::vector<uint8_t> mark((size_t)std::max(h.nmp1, 1), 0);
+    h.n_set = d.n_set_mp;
+    for (int i = 0; i < d.n_set_mp; i++) {
+        const int p = d.set_mp_idx[i];
+        GF_CHECK(p >= 0 && p < h.nmp0, GF_ERR_ARG, at + "rewritten point out of range");
+        GF_CHECK(!mark[p], GF_ERR_ARG, at + "point " + std::to_string(p) + " rewritten twice");
+        mark[p] = 1;
+    }
+    GF_CHECK(d.n_bad_mp <= M && d.n_bad_kf <= KC, GF_ERR_ARG, at + "bad list longer than the capacity");
+    h.n_bad_mp = d.n_bad_mp;
+    h.n_bad_kf = d.n_bad_kf;
+    for (int i = 0; i < d.n_bad_mp; i++)
+        GF_CHECK(d.bad_mp[i] >= 0 && d.bad_mp[i] < h.nmp1, GF_ERR_ARG, at + "bad point out of range");
+    for (int i = 0; i < d.n_bad_kf; i++)
+        GF_CHECK(d.bad_kf[i] >= 0 && d.bad_kf[i] < h.nkf1, GF_ERR_ARG, at + "bad keyframe out of range");
+    // appended keyframes
+    const std::vector<int32_t>& hs = fe->h_slots[b];
+    long long ns0 = 0;
+    for (int k = 0; k < h.nkf0; k++) ns0 += hs[k];
+    h.ns0 = (int32_t)ns0;
+    long long nnew = 0;
+    if (d.n_new_kf) {
+        GF_CHECK(d.new_kf_off[0] == 0, GF_ERR_ARG, at + "keyframe offsets must start at 0");
+        for (int k = 0; k < d.n_new_kf; k++)
+            GF_CHECK(d.new_kf_off[k] <= d.new_kf_off[k + 1], GF_ERR_ARG, at + "keyframe offsets must be ascending");
+        nnew = d.new_kf_off[d.n_new_kf];
+        GF_CHECK(nnew == 0 || d.new_kf_mp, GF_ERR_ARG, at + "null slot array");
+    }
+    GF_CHECK(ns0 + nnew <= (long long)fe->slot_cap, GF_ERR_CAP, at + "more keyframe slots than the capacity");
+    h.ns1 = (int32_t)(ns0 + nnew);
+    for (long long i = 0; i < nnew; i++)
+        GF_CHECK(d.new_kf_mp[i] >= -1 && d.new_kf_mp[i] < h.nmp1, GF_ERR_ARG, at + "keyframe slot out of range");
+    P.kf_off.resize(d.n_new_kf + 1);
+    for (int k = 0; k <= d.n_new_kf; k++) P.kf_off[k] = h.ns0 + (d.n_new_kf ? d.new_kf_off[k] : 0);
+    // slot writes: position in the stream's kf_mp from the host's slot counts
+    std::vector<int32_t> base((size_t)h.nkf0 + 1, 0);
+    for (int k = 0; k < h.nkf0; k++) base[k + 1] = base[k] + hs[k];
+    h.n_slot = d.n_slot;
+    P.slot_pos.resize(d.n_slot);
+    for (int i = 0; i < d.n_slot; i++) {
+        const int k = d.slot_kf[i], idx = d.slot_idx[i], v = d.slot_val[i];
+        GF_CHECK(k >= 0 && k < h.nkf0 && idx >= 0 && idx < hs[k], GF_ERR_ARG, at + "slot write outside the keyframes");
+        GF_CHECK(v >= -1 && v < h.nmp1, GF_ERR_ARG, at + "slot value out of range");
+        P.slot_pos[i] = base[k] + idx;
+    }
+    {
+        std::vector<int32_t> srt(P.slot_pos);
+        std::sort(srt.begin(), srt.end());
+        GF_CHECK(std::adjacent_find(srt.begin(), srt.end()) == srt.end(), GF_ERR_ARG, at + "a slot is written twice");
+    }
+    // replaced observation rows
+    const std::vector<int32_t>& ol = fe->h_obs_len[b];
+    long long no0 = 0;
+    for (int p = 0; p < h.nmp0; p++) no0 += ol[p];
+    long long no1 = no0;
+    P.row_of.assign((size_t)h.nmp1, -1);
+    if (d.n_obs_rows) GF_CHECK(d.obs_off[0] == 0, GF_ERR_ARG, at + "observation offsets must start at 0");
+    for (int r = 0; r < d.n_obs_rows; r++) {
+        const int p = d.obs_mp[r];
+        GF_CHECK(p >= 0 && p < h.nmp1, GF_ERR_ARG, at + "observation row of a point out of range");
+        GF_CHECK(P.row_of[p] < 0, GF_ERR_ARG, at + "two observation rows for point " + std::to_string(p));
+        P.row_of[p] = r;
+        const int o0 = d.obs_off[r], o1 = d.obs_off[r + 1];
+        GF_CHECK(o0 <= o1, GF_ERR_ARG, at + "observation offsets must be ascending");
+        GF_CHECK(o1 == o0 || d.obs_kf, GF_ERR_ARG, at + "null observation array");
+        for (int i = o0; i < o1; i++)
+            GF_CHECK(d.obs_kf[i] >= 0 && d.obs_kf[i] < h.nkf1 && (i == o0 || d.obs_kf[i - 1] < d.obs_kf[i]), GF_ERR_ARG,
+                     at + "observation rows hold ascending keyframes below the keyframe count");
+        no1 += (o1 - o0) - (p < h.nmp0 ? ol[p] : 0);
+    }
+    GF_CHECK(no1 <= (long long)fe->slot_cap, GF_ERR_CAP, at + "more observations than the capacity");
+    h.no0 = (int32_t)no0;
+    h.no1 = (int32_t)no1;
+    h.do_obs = d.n_obs_rows > 0 || d.n_new_mp > 0;
+    // covisibility lists
+    h.has_cov = d.has_cov ? 1 : 0;
+    h.nc0 = fe->h_nc[b];
+    h.nc1 = h.nc0;
+    if (d.has_cov) {
+        GF_CHECK(d.kf_cov_off[0] == 0, GF_ERR_ARG, at + "covisibility offsets must start at 0");
+        for (int k = 0; k < h.nkf1; k++)
+            GF_CHECK(d.kf_cov_off[k] <= d.kf_cov_off[k + 1], GF_ERR_ARG, at + "covisibility offsets must be ascending");
+        const long long nc = d.kf_cov_off[h.nkf1];
+        GF_CHECK(nc <= (long long)h.nkf1 * h.nkf1, GF_ERR_CAP, at + "more covisibility entries than keyframes squared");
+        GF_CHECK(nc == 0 || d.kf_cov, GF_ERR_ARG, at + "null covisibility array");
+        for (long long i = 0; i < nc; i++)
+            GF_CHECK(d.kf_cov[i] >= 0 && d.kf_cov[i] < h.nkf1, GF_ERR_ARG, at + "bad covisible keyframe");
+        h.nc1 = (int32_t)nc;
+    }
+    return GF_OK;
+}
+
+// Staging on first use, sized from the capacities; none afterwards.
+int mu_alloc(gf_frontend* fe) {
+    if (fe->mu_stage) return GF_OK;
+    const size_t B = fe->D.B, M = fe->D.M, KC = gf_frontend::KF_CAP;
+    fe->mu_stream_bytes = mu_stream_cap_bytes(M, fe->slot_cap, KC);
+    fe->mu_bytes = fe->mu_stream_bytes * B;
+    void* p = nullptr;
+    FE_RC(fe_alloc(fe, 4 * B * (M + 1), &p));
+    fe->mu_off_new = (int32_t*)p;
+    FE_RC(fe_alloc(fe, 4 * B * fe->slot_cap, &p));
+    fe->mu_obs_new = (int32_t*)p;
+    for (int i = 0; i < 2; i++) {
+        GF_HIP(hipHostMalloc((void**)&fe->mu_pin[i], fe->mu_bytes, hipHostMallocDefault));
+        GF_HIP(hipEventCreateWithFlags(&fe->mu_ev[i], hipEventDisableTiming));
+    }
+    FE_RC(fe_alloc(fe, fe->mu_bytes, &p));
+    fe->mu_stage = (uint8_t*)p;  // last: marks the staging as complete
+    return GF_OK;
+}
+
+}  // namespace
+
+int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* deltas) {
+    GF_CHECK(fe && ndelta >= 0 && (ndelta == 0 || deltas), GF_ERR_ARG, "bad arguments");
+    if (ndelta == 0) return GF_OK;
+    GF_CHECK(fe->covis_set, GF_ERR_ARG, "map feedback needs keyframe graphs (gf_frontend_set_covis)");
+    GF_CHECK(!fe->extracted, GF_ERR_ARG, "the extracted frame has not been tracked (gf_frontend_step_track)");
+    const int B = fe->D.B, M = fe->D.M;
+    GF_CHECK(ndelta <= B, GF_ERR_ARG, "a stream is named at most once");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    hipStream_t s = fe->ctx->stream;
+    std::vector<uint8_t> named(B, 0);
+    for (int i = 0; i < ndelta; i++) {
+        const int b = deltas[i].stream;
+        GF_CHECK(b >= 0 && b < B, GF_ERR_ARG, "bad stream");
+        GF_CHECK(!named[b], GF_ERR_ARG, "stream " + std::to_string(b) + " is named twice");
+        named[b] = 1;
+        if (fe->h_nmp[b] < 0) {  // the size was written behind the host's back (gf_dist_bcast_map)
+            GF_HIP(hipStreamSynchronize(s));
+            int32_t n = 0;
+            GF_HIP(hipMemcpy(&n, fe->g_nmp + b, 4, hipMemcpyDeviceToHost));
+            fe->h_nmp[b] = n;
+        }
+    }
+    // validate every delta before anything is written
+    std::vector<MuPlan> plans(ndelta);
+    for (int i = 0; i < ndelta; i++) FE_RC(mu_validate(fe, deltas[i], plans[i]));
+    FE_RC(mu_alloc(fe));
+    // pack: headers, then every stream's sections
+    const int turn = fe->mu_turn;
+    GF_HIP(hipEventSynchronize(fe->mu_ev[turn]));  // the upload that last used this buffer (two calls ago)
+    uint8_t* pin = fe->mu_pin[turn];
+    size_t at = mu_a16(sizeof(gf::MuHdr) * (size_t)ndelta);
+    auto put = [&](const void* src, size_t bytes, size_t room) -> int64_t {
+        const size_t o = at;
+        if (bytes) memcpy(pin + o, src, bytes);
+        if (room > bytes) memset(pin + o + bytes, 0, room - bytes);
+        at += mu_a16(std::max(room, bytes));
+        return (int64_t)o;
+    };
+    gf::MapUpdateShape sh;
+    for (int i = 0; i < ndelta; i++) {
+        const gf_map_delta& d = deltas[i];
+        MuPlan& P = plans[i];
+        gf::MuHdr& h = P.h;
+        const size_t nn = d.n_new_mp, nsn = h.ns1 - h.ns0;
+        h.new_mp = put(d.new_mp, sizeof(gf_map_point) * nn, 0);
+        h.new_desc = put(d.new_mp_desc, 32 * nn, 0);
+        h.new_bad = put(d.new_mp_bad, d.new_mp_bad ? nn : 0, nn);
+        h.set_idx = put(d.set_mp_idx, 4 * (size_t)d.n_set_mp, 0);
+        h.set_mp = put(d.set_mp, sizeof(gf_map_point) * (size_t)d.n_set_mp, 0);
+        h.set_desc = put(d.set_mp_desc, 32 * (size_t)d.n_set_mp, 0);
+        h.bad_mp = put(d.bad_mp, 4 * (size_t)d.n_bad_mp, 0);
+        h.bad_kf = put(d.bad_kf, 4 * (size_t)d.n_bad_kf, 0);
+        h.kf_off = put(P.kf_off.data(), 4 * P.kf_off.size(), 0);
+        h.kf_mp = put(d.new_kf_mp, 4 * nsn, 0);
+        h.kf_bad = put(d.new_kf_bad, d.new_kf_bad ? (size_t)d.n_new_kf : 0, (size_t)d.n_new_kf);
+        h.slot_pos = put(P.slot_pos.data(), 4 * (size_t)d.n_slot, 0);
+        h.slot_val = put(d.slot_val, 4 * (size_t)d.n_slot, 0);
+        h.row_of = put(P.row_of.data(), 4 * P.row_of.size(), 0);
+        const size_t nro = d.n_obs_rows ? (size_t)d.obs_off[d.n_obs_rows] : 0;
+        h.obs_off = put(d.obs_off, d.n_obs_rows ? 4 * ((size_t)d.n_obs_rows + 1) : 0, 4 * ((size_t)d.n_obs_rows + 2));
+        h.obs_kf = put(d.obs_kf, 4 * nro, 0);
+        h.cov_off = put(d.kf_cov_off, d.has_cov ? 4 * ((size_t)h.nkf1 + 1) : 0, 0);
+        h.cov = put(d.kf_cov, d.has_cov ? 4 * (size_t)h.nc1 : 0, 0);
+        memcpy(pin + sizeof(gf::MuHdr) * (size_t)i, &h, sizeof(h));
+        sh.new_mp = std::max(sh.new_mp, d.n_new_mp);
+        sh.set_mp = std::max(sh.set_mp, d.n_set_mp);
+        sh.new_slots = std::max(sh.new_slots, (int)nsn);
+        sh.slot_writes = std::max(sh.slot_writes, d.n_slot);
+        sh.cov = std::max(sh.cov, d.has_cov ? h.nc1 : 0);
+        sh.any_new_kf |= d.n_new_kf > 0;
+        sh.any_cov |= d.has_cov != 0;
+        if (h.do_obs) {
+            sh.any_obs = true;
+            sh.nmp1 = std::max(sh.nmp1, h.nmp1);
+            sh.no1 = std::max(sh.no1, h.no1);
+        }
+    }
+    GF_CHECK(at <= fe->mu_bytes, GF_ERR_CAP, "the deltas exceed the staging sized from the capacities");
+    // the host mirrors follow the device tables
+    for (int i = 0; i < ndelta; i++) {
+        const gf_map_delta& d = deltas[i];
+        const gf::MuHdr& h = plans[i].h;
+        const int b = h.stream;
+        fe->h_nmp[b] = h.nmp1;
+        fe->h_kfc[b] = h.nkf1;
+        fe->h_nc[b] = h.nc1;
+        for (int k = 0; k < d.n_new_kf; k++) fe->h_slots[b].push_back(d.new_kf_off[k + 1] - d.new_kf_off[k]);
+        fe->h_obs_len[b].resize(h.nmp1, 0);
+        for (int r = 0; r < d.n_obs_rows; r++) fe->h_obs_len[b][d.obs_mp[r]] = d.obs_off[r + 1] - d.obs_off[r];
+    }
+    GF_HIP(hipMemcpyAsync(fe->mu_stage, pin, at, hipMemcpyHostToDevice, s));
+    GF_HIP(hipEventRecord(fe->mu_ev[turn], s));
+    fe->mu_turn = turn ^ 1;
+    FeDev& D = fe->D;
+    gf::MapUpdateArgs A{};
+    A.stage = fe->mu_stage;
+    A.L = ndelta;
+    A.M = M;
+    A.cap = D.cap;
+    A.kf_cap = gf_frontend::KF_CAP;
+    A.slot_cap = (long long)fe->slot_cap;
+    A.map = (gf_map_point*)fe->gm.map;
+    A.desc = (uint8_t*)fe->gm.desc;
+    A.pos = (float*)fe->gm.pos;
+    A.upd = fe->gm.upd;
+    A.views = fe->gm.views;
+    A.nmp = fe->g_nmp;
+    A.kfc = fe->d_kfc;
+    A.covis = fe->d_covis;
+    A.kf_bad = fe->cv_kf_bad;
+    A.mp_bad = fe->cv_mp_bad;
+    A.kf_mp_off = fe->cv_kf_mp_off;
+    A.kf_mp = fe->cv_kf_mp;
+    A.kf_cov_off = fe->cv_kf_cov_off;
+    A.kf_cov = fe->cv_kf_cov;
+    A.mp_obs_off = fe->cv_mp_obs_off;
+    A.mp_obs = fe->cv_mp_obs;
+    A.last_kp2mp = D.last_kp2mp;
+    A.last_nkp = D.last_nkp;
+    A.last_pos = D.last_pos;
+    A.obs_off_new = fe->mu_off_new;
+    A.obs_new = fe->mu_obs_new;
+    return gf::map_update_launch(fe->ctx, A, sh, s);
+}
+
+int gf_frontend_get_covis(gf_frontend* fe, int stream, int32_t* counts, const gf_covis_out* out, const int32_t* caps) {
+    GF_CHECK(fe && counts && stream >= 0 && stream < fe->D.B, GF_ERR_ARG, "bad arguments");
+    GF_CHECK(fe->covis_set && fe->has_covis[stream], GF_ERR_ARG, "the stream has no keyframe graph");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    const size_t b = stream, M = fe->D.M, KC = gf_frontend::KF_CAP;
+    gf_covis_map d{};
+    GF_HIP(hipMemcpy(&d, fe->d_covis + b, sizeof(d), hipMemcpyDeviceToHost));
+    const int nkf = d.nkf, nmp = d.nmp;
+    GF_CHECK(nkf >= 0 && nkf <= (int)KC && nmp >= 0 && nmp <= (int)M, GF_ERR_HIP, "graph sizes out of range on the device");
+    std::vector<int32_t> ko(nkf + 1, 0), co(nkf + 1, 0), oo(nmp + 1, 0);
+    if (nkf) {
+        GF_HIP(hipMemcpy(ko.data(), fe->cv_kf_mp_off + b * (KC + 1), 4 * ko.size(), hipMemcpyDeviceToHost));
+        GF_HIP(hipMemcpy(co.data(), fe->cv_kf_cov_off + b * (KC + 1), 4 * co.size(), hipMemcpyDeviceToHost));
+    }
+    if (nmp) GF_HIP(hipMemcpy(oo.data(), fe->cv_mp_obs_off + b * (M + 1), 4 * oo.size(), hipMemcpyDeviceToHost));
+    const int ns = ko[nkf], nc = co[nkf], no = oo[nmp];
+    GF_CHECK(ns >= 0 && (size_t)ns <= fe->slot_cap && nc >= 0 && (size_t)nc <= KC * KC && no >= 0 &&
+                 (size_t)no <= fe->slot_cap,
+             GF_ERR_HIP, "graph offsets out of range on the device");
+    counts[0] = nkf;
+    counts[1] = nmp;
+    counts[2] = ns;
+    counts[3] = nc;
+    counts[4] = no;
+    if (!out) return GF_OK;
+    GF_CHECK(caps, GF_ERR_ARG, "null capacities");
+    GF_CHECK(ns <= caps[0] && nc <= caps[1] && no <= caps[2], GF_ERR_CAP, "graph larger than the output capacity");
+    GF_CHECK(out->kf_bad && out->kf_mp_off && out->kf_mp && out->kf_cov_off && out->kf_cov && out->mp_bad &&
+                 out->mp_obs_off && out->mp_obs,
+             GF_ERR_ARG, "null output array");
+    auto down = [](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    memcpy(out->kf_mp_off, ko.data(), 4 * ko.size());
+    memcpy(out->kf_cov_off, co.data(), 4 * co.size());
+    memcpy(out->mp_obs_off, oo.data(), 4 * oo.size());
+    GF_HIP(down(out->kf_bad, fe->cv_kf_bad + b * KC, nkf));
+    GF_HIP(down(out->kf_mp, fe->cv_kf_mp + b * fe->slot_cap, 4 * (size_t)ns));
+    GF_HIP(down(out->kf_cov, fe->cv_kf_cov + b * KC * KC, 4 * (size_t)nc));
+    GF_HIP(down(out->mp_bad, fe->cv_mp_bad + b * M, nmp));
+    GF_HIP(down(out->mp_obs, fe->cv_mp_obs + b * fe->slot_cap, 4 * (size_t)no));
     return GF_OK;
 }
 
@@ -2227,6 +2587,7 @@ extern "C" int gf_dist_bcast_map(gf_dist* d, gf_frontend* fe, int root) {
         (rc = gf::dist_bcast(d, (void*)fe->gm.pos, sizeof(float) * 3 * (size_t)fe->D.B * fe->D.M, root)))
         return rc;
     GF_HIP(hipStreamSynchronize(gf::dist_ctx(d)->stream));
+    if (gf::dist_rank(d) != root) fe->h_nmp.assign(fe->D.B, -1);  // read back by gf_frontend_update_maps
     if (gf::dist_rank(d) != root) {
         const size_t n = (size_t)fe->D.B * fe->D.M;
         std::vector<int32_t> neg(n, -1000);

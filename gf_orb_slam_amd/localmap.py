@@ -47,6 +47,92 @@ class CovisGraph:
         return DeviceCovisGraph(self, device)
 
 
+class CovisOut(ctypes.Structure):
+    """gf_covis_out."""
+
+    _fields_ = [(k, _P) for k, _ in _ARRAYS]
+
+
+class MapDeltaStruct(ctypes.Structure):
+    """gf_map_delta."""
+
+    _I = ctypes.c_int32
+    _fields_ = [("stream", _I), ("n_new_mp", _I), ("new_mp", _P), ("new_mp_desc", _P), ("new_mp_bad", _P),
+                ("n_set_mp", _I), ("set_mp_idx", _P), ("set_mp", _P), ("set_mp_desc", _P), ("n_bad_mp", _I),
+                ("bad_mp", _P), ("n_new_kf", _I), ("new_kf_off", _P), ("new_kf_mp", _P), ("new_kf_bad", _P),
+                ("n_bad_kf", _I), ("bad_kf", _P), ("n_slot", _I), ("slot_kf", _P), ("slot_idx", _P), ("slot_val", _P),
+                ("n_obs_rows", _I), ("obs_mp", _P), ("obs_off", _P), ("obs_kf", _P), ("has_cov", _I),
+                ("kf_cov_off", _P), ("kf_cov", _P)]
+
+
+class MapDelta:
+    """Host arrays of one stream's map delta (abi.h gf_map_delta), what the
+    mapper wrote since the tracker last looked, in the front end's indices:
+    new_mp / new_mp_desc / new_mp_bad: appended points; set_mp_idx / set_mp /
+    set_mp_desc: rewritten points; bad_mp: points turned bad; new_kf: a list of
+    slot rows, new_kf_bad: appended keyframes; bad_kf: keyframes turned bad;
+    slot_kf / slot_idx / slot_val: slot writes on existing keyframes; obs_rows:
+    {point: ascending observing keyframes}, the whole new row of every touched
+    point; kf_cov: a list of the ordered covisible keyframes of every keyframe
+    (old and appended), or None when the lists are unchanged."""
+
+    def __init__(self, stream: int, new_mp=None, new_mp_desc=None, new_mp_bad=None, set_mp_idx=None, set_mp=None,
+                 set_mp_desc=None, bad_mp=None, new_kf=None, new_kf_bad=None, bad_kf=None, slot_kf=None, slot_idx=None,
+                 slot_val=None, obs_rows=None, kf_cov=None):
+        from .matcher import MAP_POINT_DTYPE
+
+        def arr(a, dt, shape=(-1,)):
+            return np.ascontiguousarray(np.zeros(0, dt) if a is None else a, dt).reshape(shape)
+
+        self.stream = int(stream)
+        self.new_mp = arr(new_mp, MAP_POINT_DTYPE)
+        self.new_mp_desc = arr(new_mp_desc, np.uint8, (-1, 32))
+        self.new_mp_bad = (np.zeros(len(self.new_mp), np.uint8) if new_mp_bad is None
+                           else arr(np.asarray(new_mp_bad).astype(np.uint8), np.uint8))
+        self.set_mp_idx = arr(set_mp_idx, np.int32)
+        self.set_mp = arr(set_mp, MAP_POINT_DTYPE)
+        self.set_mp_desc = arr(set_mp_desc, np.uint8, (-1, 32))
+        self.bad_mp, self.bad_kf = arr(bad_mp, np.int32), arr(bad_kf, np.int32)
+        rows = [np.asarray(r, np.int32).reshape(-1) for r in (new_kf or [])]
+        self.new_kf_off = np.zeros(len(rows) + 1, np.int32)
+        self.new_kf_off[1:] = np.cumsum([len(r) for r in rows])
+        self.new_kf_mp = arr(np.concatenate(rows) if rows else None, np.int32)
+        self.new_kf_bad = (np.zeros(len(rows), np.uint8) if new_kf_bad is None
+                           else arr(np.asarray(new_kf_bad).astype(np.uint8), np.uint8))
+        self.slot_kf, self.slot_idx, self.slot_val = arr(slot_kf, np.int32), arr(slot_idx, np.int32), arr(slot_val,
+                                                                                                             np.int32)
+        obs_rows = obs_rows or {}
+        pts = list(obs_rows)
+        self.obs_mp = arr(pts, np.int32)
+        orow = [np.asarray(obs_rows[p], np.int32).reshape(-1) for p in pts]
+        self.obs_off = np.zeros(len(pts) + 1, np.int32)
+        self.obs_off[1:] = np.cumsum([len(r) for r in orow])
+        self.obs_kf = arr(np.concatenate(orow) if orow else None, np.int32)
+        self.has_cov = kf_cov is not None
+        crow = [np.asarray(c, np.int32).reshape(-1) for c in (kf_cov or [])]
+        self.kf_cov_off = np.zeros(len(crow) + 1, np.int32)
+        self.kf_cov_off[1:] = np.cumsum([len(c) for c in crow])
+        self.kf_cov = arr(np.concatenate(crow) if crow else None, np.int32)
+        if not (len(self.new_mp) == len(self.new_mp_desc) == len(self.new_mp_bad) and
+                len(self.set_mp_idx) == len(self.set_mp) == len(self.set_mp_desc) and
+                len(self.slot_kf) == len(self.slot_idx) == len(self.slot_val) and len(self.new_kf_bad) == len(rows)):
+            raise ValueError("map delta: arrays of one item differ in length")
+
+    def empty(self) -> bool:
+        return not (len(self.new_mp) or len(self.set_mp_idx) or len(self.bad_mp) or len(self.bad_kf) or
+                    len(self.new_kf_off) > 1 or len(self.slot_kf) or len(self.obs_mp) or self.has_cov)
+
+    def struct(self) -> MapDeltaStruct:
+        p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        return MapDeltaStruct(
+            self.stream, len(self.new_mp), p(self.new_mp), p(self.new_mp_desc), p(self.new_mp_bad),
+            len(self.set_mp_idx), p(self.set_mp_idx), p(self.set_mp), p(self.set_mp_desc), len(self.bad_mp),
+            p(self.bad_mp), len(self.new_kf_off) - 1, self.new_kf_off.ctypes.data, p(self.new_kf_mp),
+            p(self.new_kf_bad), len(self.bad_kf), p(self.bad_kf), len(self.slot_kf), p(self.slot_kf), p(self.slot_idx),
+            p(self.slot_val), len(self.obs_mp), p(self.obs_mp), self.obs_off.ctypes.data, p(self.obs_kf),
+            int(self.has_cov), self.kf_cov_off.ctypes.data, p(self.kf_cov))
+
+
 class DeviceCovisGraph:
     """The same arrays resident on the device (torch allocations as plumbing)."""
 

@@ -349,6 +349,36 @@ class FrontEnd:
         self._graphs[stream] = g
         check(lib().gf_frontend_set_covis(self.handle, stream, ctypes.byref(g.struct())))
 
+    def update_maps(self, deltas) -> None:
+        """gf_frontend_update_maps: apply the mapper's changes (a
+        localmap.MapDelta or a list of them, one per stream at most) to the
+        stream maps and keyframe graphs in place, behind the last step, without
+        a host synchronisation; legal after capture_graph(). A refused delta
+        (GFError) leaves every stream of the call untouched."""
+        from .localmap import MapDelta, MapDeltaStruct
+
+        ds = [deltas] if isinstance(deltas, MapDelta) else list(deltas)
+        if not ds:
+            return
+        arr = (MapDeltaStruct * len(ds))(*[d.struct() for d in ds])
+        check(lib().gf_frontend_update_maps(self.handle, len(ds), arr))
+
+    def covis(self, stream: int) -> dict:
+        """gf_frontend_get_covis: the keyframe graph the front end holds for
+        the stream, as the dict of arrays set_covis takes."""
+        from .localmap import _ARRAYS, CovisOut
+
+        counts = np.zeros(5, np.int32)
+        check(lib().gf_frontend_get_covis(self.handle, stream, ptr(counts), None, None))
+        nkf, nmp, ns, nc, no = (int(c) for c in counts)
+        size = dict(kf_bad=nkf, kf_mp_off=nkf + 1, kf_mp=ns, kf_cov_off=nkf + 1, kf_cov=nc, mp_bad=nmp,
+                    mp_obs_off=nmp + 1, mp_obs=no)
+        buf = {k: np.zeros(max(size[k], 1), dt) for k, dt in _ARRAYS}
+        out = CovisOut(*[buf[k].ctypes.data for k, _ in _ARRAYS])
+        caps = np.array([max(ns, 1), max(nc, 1), max(no, 1)], np.int32)
+        check(lib().gf_frontend_get_covis(self.handle, stream, ptr(counts), ctypes.byref(out), ptr(caps)))
+        return {k: buf[k][:size[k]].copy() for k, _ in _ARRAYS}
+
     def set_rng(self, stream: int, seed: int) -> None:
         check(lib().gf_frontend_set_rng(self.handle, stream, ctypes.c_uint32(seed)))
 

@@ -451,14 +451,15 @@ class MonoInitializer:
 
 
 # ------------------------------------------------ NeedNewKeyFrame / CreateNewKeyFrame -> LocalMapping
-def loopmap_from_global_map(info, gm, voc=None, ctx=None, levelsup: int = 4):
+def loopmap_from_global_map(info, gm, voc=None, ctx=None, levelsup: int = 4, counter=None):
     """A ``LoopMap`` over a ``scene.build_global_map`` entry ``gm``, the map a
     front-end stream tracks (``FrontEnd.set_map`` / ``set_covis`` of the same
     entry): point id = map index, keyframe index = graph index, the slot
     tables from the graph's CSR, the poses ``gm["kf_Tcw"]``. With ``voc``
     every keyframe gets its ``ComputeBoW`` (what CreateNewMapPoints reads of
     the neighbours); the covisibility graph is ``UpdateConnections`` of every
-    keyframe, in index order."""
+    keyframe, in index order (``counter``: as ``LoopMap.update_connections_batch``
+    takes it, the device's by default)."""
     from .bow import FeatureVector
     from .loopmap import LoopMap
 
@@ -473,8 +474,125 @@ def loopmap_from_global_map(info, gm, voc=None, ctx=None, levelsup: int = 4):
             words, values, fv = transform(m.kf_desc[k], levelsup)
             m.kf_bow[k] = (words, values)
             m.kf_fv[k] = fv if isinstance(fv, FeatureVector) else FeatureVector(*fv)
-    m.update_connections_batch(range(m.nkf), ctx)
+    m.update_connections_batch(range(m.nkf), ctx, counter)
     return m
+
+
+# ------------------------------------------------ LocalMapping -> the tracker's map
+def _csr(rows, dtype=np.int32):
+    off = np.zeros(len(rows) + 1, np.int32)
+    if rows:
+        off[1:] = np.cumsum([len(r) for r in rows])
+    flat = np.concatenate([np.asarray(r, dtype).reshape(-1) for r in rows]) if rows else np.zeros(0, dtype)
+    return off, np.ascontiguousarray(flat, dtype)
+
+
+def covis_graph_from_loopmap(m) -> dict:
+    """The ``gf_covis_map`` arrays of a ``LoopMap`` (the dict
+    ``FrontEnd.set_covis`` takes), point id = map index and keyframe index =
+    graph index: the slot tables, the observation maps as rows of ascending
+    keyframe index, ``kf_cov`` the ordered connected keyframes
+    (mvpOrderedConnectedKeyFrames). The inverse of
+    :func:`loopmap_from_global_map`."""
+    kf_mp_off, kf_mp = _csr([np.asarray(s, np.int32) for s in m.slots])
+    kf_cov_off, kf_cov = _csr([np.asarray(o, np.int32) for o in m.ordered])
+    mp_obs_off, mp_obs = _csr([np.asarray(sorted(o), np.int32) for o in m.obs])
+    return dict(kf_bad=np.asarray(m.kf_bad).astype(np.uint8), kf_mp_off=kf_mp_off, kf_mp=kf_mp, kf_cov_off=kf_cov_off,
+                kf_cov=kf_cov, mp_bad=np.asarray(m.mp_bad).astype(np.uint8), mp_obs_off=mp_obs_off, mp_obs=mp_obs)
+
+
+def _changed_rows(off_a, flat_a, off_b, flat_b, n: int) -> np.ndarray:
+    """Rows < n of two CSR tables that differ in length or content."""
+    la, lb = np.diff(off_a[:n + 1]), np.diff(off_b[:n + 1])
+    diff = la != lb
+    same = np.nonzero(~diff & (la > 0))[0]
+    if len(same):
+        ln = la[same]
+        row = np.repeat(np.arange(len(same)), ln)
+        within = np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln)
+        ne = flat_a[off_a[same][row] + within] != flat_b[off_b[same][row] + within]
+        bad = np.zeros(len(same), bool)
+        np.logical_or.at(bad, row, ne)
+        diff[same[bad]] = True
+    return np.nonzero(diff)[0]
+
+
+class MapFeedback:
+    """Carries a ``LocalMapper``'s result back into the map a front-end stream
+    tracks (``FrontEnd.update_maps``): a host shadow of what the front end
+    holds for the stream (points, descriptors, bad flags, slot rows,
+    observation rows, covisibility lists), ``delta()`` the difference between
+    the ``LoopMap`` and the shadow as a ``localmap.MapDelta``, ``commit()``
+    the shadow advanced after the update succeeded.
+
+    The id mapping is the identity: the LoopMap's point id is the map index,
+    its keyframe index the graph index, and both only grow. Anything else (a
+    map smaller than the shadow, an existing keyframe whose slot count changed,
+    a bad point or keyframe that is good again) raises ``ValueError``.
+
+    The shadow starts from the front end's own state (``fe.read`` /
+    ``fe.covis``), or from ``shadow`` = dict(mp, desc, graph) when given."""
+
+    def __init__(self, fe, stream: int, loopmap, shadow=None):
+        self.fe, self.stream, self.map = fe, int(stream), loopmap
+        if shadow is None:
+            n = int(fe.read("nmp")[stream])
+            shadow = dict(mp=fe.read("map")[stream][:n], desc=fe.read("map_desc")[stream][:n], graph=fe.covis(stream))
+        self.mp = np.ascontiguousarray(shadow["mp"], MAP_POINT_DTYPE).copy()
+        self.desc = np.ascontiguousarray(shadow["desc"], np.uint8).reshape(-1, 32).copy()
+        self.graph = {k: np.array(v, copy=True) for k, v in shadow["graph"].items()}
+        if len(self.graph["mp_bad"]) != len(self.mp):
+            raise ValueError("the shadow's graph and points differ in size")
+        self._next = None
+        self.delta()  # raises where the map and the front end cannot share indices
+        self._next = None
+
+    def delta(self):
+        """The ``MapDelta`` that takes the front end from the shadow to the
+        LoopMap as it stands."""
+        from .localmap import MapDelta
+
+        m, g0 = self.map, self.graph
+        g1 = covis_graph_from_loopmap(m)
+        n0, n1, k0, k1 = len(self.mp), len(m.mps), len(g0["kf_bad"]), m.nkf
+        if n1 < n0 or k1 < k0:
+            raise ValueError("the map holds fewer points or keyframes than the front end: not the identity mapping")
+        ns0 = int(g0["kf_mp_off"][k0])
+        if not np.array_equal(g1["kf_mp_off"][:k0 + 1], g0["kf_mp_off"]):
+            raise ValueError("an existing keyframe changed its slot count: not the identity mapping")
+        if np.any(g0["mp_bad"].astype(bool) & ~g1["mp_bad"][:n0].astype(bool)) or \
+                np.any(g0["kf_bad"].astype(bool) & ~g1["kf_bad"][:k0].astype(bool)):
+            raise ValueError("a bad point or keyframe is good again")
+        mp1 = np.ascontiguousarray(m.mps, MAP_POINT_DTYPE)
+        desc1 = np.ascontiguousarray(m.mp_desc, np.uint8).reshape(-1, 32)
+        rows = lambda a: a.view(np.uint8).reshape(len(a), -1)  # noqa: E731
+        ch = np.nonzero(np.any(rows(mp1[:n0]) != rows(self.mp), axis=1) | np.any(desc1[:n0] != self.desc, axis=1))[0]
+        bad_mp = np.nonzero(g1["mp_bad"][:n0].astype(bool) & ~g0["mp_bad"].astype(bool))[0]
+        bad_kf = np.nonzero(g1["kf_bad"][:k0].astype(bool) & ~g0["kf_bad"].astype(bool))[0]
+        pos = np.nonzero(g1["kf_mp"][:ns0] != g0["kf_mp"][:ns0])[0]
+        skf = np.searchsorted(g0["kf_mp_off"], pos, side="right") - 1
+        touched = _changed_rows(g1["mp_obs_off"], g1["mp_obs"], g0["mp_obs_off"], g0["mp_obs"], n0)
+        o1 = g1["mp_obs_off"]
+        grown = n0 + np.nonzero(np.diff(o1[n0:]) > 0)[0]
+        obs_rows = {int(p): g1["mp_obs"][o1[p]:o1[p + 1]] for p in np.concatenate([touched, grown])}
+        same_cov = (np.array_equal(g1["kf_cov_off"][:k0 + 1], g0["kf_cov_off"]) and
+                    np.array_equal(g1["kf_cov"], g0["kf_cov"]) and int(g1["kf_cov_off"][k1]) == len(g0["kf_cov"]))
+        co = g1["kf_cov_off"]
+        d = MapDelta(self.stream, new_mp=mp1[n0:], new_mp_desc=desc1[n0:], new_mp_bad=g1["mp_bad"][n0:],
+                     set_mp_idx=ch, set_mp=mp1[ch], set_mp_desc=desc1[ch], bad_mp=bad_mp,
+                     new_kf=[np.asarray(s, np.int32) for s in m.slots[k0:]], new_kf_bad=g1["kf_bad"][k0:],
+                     bad_kf=bad_kf, slot_kf=skf, slot_idx=pos - g0["kf_mp_off"][skf], slot_val=g1["kf_mp"][pos],
+                     obs_rows=obs_rows,
+                     kf_cov=None if same_cov else [g1["kf_cov"][co[k]:co[k + 1]] for k in range(k1)])
+        self._next = dict(mp=mp1.copy(), desc=desc1.copy(), graph=g1)
+        return d
+
+    def commit(self) -> None:
+        """The shadow becomes the map of the last :meth:`delta`."""
+        if self._next is None:
+            raise RuntimeError("no delta to commit")
+        self.mp, self.desc, self.graph = self._next["mp"], self._next["desc"], self._next["graph"]
+        self._next = None
 
 
 class KeyFrameInserter:
@@ -487,9 +605,14 @@ class KeyFrameInserter:
     without a mapper is left alone).
 
     point_ids[stream] (optional) maps the front end's map index to the
-    mapper's point id (identity by default; -1 stays -1)."""
+    mapper's point id (identity by default; -1 stays -1).
 
-    def __init__(self, fe, mappers, point_ids=None):
+    feedback (optional): a ``MapFeedback`` per stream (a dict or a list) over
+    the stream's mapper's map; ``feed_back()`` then carries the mappers' results
+    back into the front end's maps. Off without it; a stream with ``point_ids``
+    cannot have one (the feedback needs the identity mapping)."""
+
+    def __init__(self, fe, mappers, point_ids=None, feedback=None):
         self.fe = fe
         self.mappers = dict(mappers) if isinstance(mappers, dict) else dict(enumerate(mappers))
         self.point_ids = dict(point_ids or {})
@@ -497,6 +620,12 @@ class KeyFrameInserter:
         self.stop_flags = {b: ctypes.c_uint8(0) for b in self.mappers}  # the byte LocalBundleAdjustment polls
         self.stop_requested = {b: False for b in self.mappers}
         self.taken = []  # every keyframe handed over, in order: (stream, keyframe index, header fields)
+        fb = feedback or {}
+        self.feedback = dict(fb) if isinstance(fb, dict) else dict(enumerate(fb))
+        for b in self.feedback:
+            if self.point_ids.get(b) is not None:
+                raise ValueError(f"stream {b}: map feedback needs the identity id mapping")
+        self._ran = set()  # streams whose mapper ran since the last feed_back
 
     def pump(self) -> list:
         """Take the pending keyframes of the mapped streams' front end, insert
@@ -536,9 +665,27 @@ class KeyFrameInserter:
         self.stop_flags[stream].value = 0
         abort_ba = bool(q) or self.stop_requested[stream]
         rep = self.mappers[stream].step(cur, abort_ba=abort_ba, stop_flag=self.stop_flags[stream])
+        self._ran.add(stream)
         if not q:
             self.fe.set_keyframe_state(stream, accept=1)
         return rep
+
+    def feed_back(self, streams=None) -> list:
+        """The maps of the streams whose mapper ran since the last call (or of
+        ``streams``) back into the front end: their ``MapFeedback.delta()``s in
+        one ``FrontEnd.update_maps`` call, the shadows committed after it. In
+        the reference this is no step at all: Tracking reads what LocalMapping
+        wrote through its pointers, under the map mutex. -> the deltas sent."""
+        which = sorted(self._ran if streams is None else streams)
+        fbs = [self.feedback[b] for b in which if b in self.feedback]
+        deltas = [fb.delta() for fb in fbs]
+        live = [(fb, d) for fb, d in zip(fbs, deltas) if not d.empty()]
+        if live:
+            self.fe.update_maps([d for _, d in live])
+        for fb in fbs:
+            fb.commit()
+        self._ran -= set(which)
+        return [d for _, d in live]
 
     def request_stop(self, stream: int) -> None:
         """LocalMapping::RequestStop (:132-135): the stream inserts no keyframe

@@ -2025,6 +2025,101 @@ int gf_frontend_write(gf_frontend* fe, int field, const void* host, size_t bytes
 /* Size and device pointer of a field. */
 int gf_frontend_field(gf_frontend* fe, int field, size_t* bytes, void** d_ptr);
 
+/* ------------------------------------------------------------ map feedback
+ * What LocalMapping wrote into the map since the tracker last looked, for one
+ * stream, in the front end's own indices (map index, graph keyframe index;
+ * both append-only, so every index the front end holds stays valid). In the
+ * reference Tracking reads these through MapPoint* / KeyFrame* (Tracking.cc:
+ * 3689-3852): here they are applied to the stream's map and keyframe graph in
+ * place, on the context's stream behind the last step. Host arrays; an array
+ * whose count is 0 may be NULL.
+ *   new_mp / new_mp_desc / new_mp_bad [n_new_mp]: Map::AddMapPoint; they take
+ *     the indices nmp .. nmp + n_new_mp - 1 with the per-point state of a
+ *     fresh point (GF_FE_MP_UPD -1000, GF_FE_VIEWS 0). new_mp_bad NULL: none.
+ *   set_mp_idx / set_mp / set_mp_desc [n_set_mp]: SetWorldPos,
+ *     UpdateNormalAndDepth and ComputeDistinctiveDescriptors of existing points
+ *     (distinct indices < nmp); GF_FE_MP_H / MP_INFO / MP_UV / MP_UPD / VIEWS of
+ *     the point stay as they are.
+ *   bad_mp [n_bad_mp]: MapPoint::SetBadFlag / Replace: mp_bad = 1 (indices <
+ *     nmp + n_new_mp). A bad point never returns; its state rows stay.
+ *   new_kf_off [n_new_kf + 1] / new_kf_mp / new_kf_bad [n_new_kf]:
+ *     Map::AddKeyFrame; slot rows as a CSR starting at 0, appended at the tail
+ *     of kf_mp (existing rows do not move). new_kf_bad NULL: none.
+ *   bad_kf [n_bad_kf]: KeyFrame::SetBadFlag (indices < nkf + n_new_kf).
+ *   slot_kf / slot_idx / slot_val [n_slot]: AddMapPoint / ReplaceMapPointMatch /
+ *     EraseMapPointMatch on existing keyframes (kf < nkf), value -1 = NULL, at
+ *     most one write per slot.
+ *   obs_mp [n_obs_rows] / obs_off [n_obs_rows + 1] / obs_kf: the whole new
+ *     observation row (observing keyframe indices, ascending) of every touched
+ *     point, old or appended (distinct points); an untouched point keeps its row
+ *     and an appended point without a row has none.
+ *   kf_cov_off [nkf + n_new_kf + 1] / kf_cov: mvpOrderedConnectedKeyFrames of
+ *     every keyframe, when has_cov != 0; otherwise the lists stay and appended
+ *     keyframes get empty ones. */
+typedef struct gf_map_delta {
+    int32_t stream;
+    int32_t n_new_mp;
+    const gf_map_point* new_mp;
+    const uint8_t* new_mp_desc;
+    const uint8_t* new_mp_bad;
+    int32_t n_set_mp;
+    const int32_t* set_mp_idx;
+    const gf_map_point* set_mp;
+    const uint8_t* set_mp_desc;
+    int32_t n_bad_mp;
+    const int32_t* bad_mp;
+    int32_t n_new_kf;
+    const int32_t* new_kf_off;
+    const int32_t* new_kf_mp;
+    const uint8_t* new_kf_bad;
+    int32_t n_bad_kf;
+    const int32_t* bad_kf;
+    int32_t n_slot;
+    const int32_t* slot_kf;
+    const int32_t* slot_idx;
+    const int32_t* slot_val;
+    int32_t n_obs_rows;
+    const int32_t* obs_mp;
+    const int32_t* obs_off;
+    const int32_t* obs_kf;
+    int32_t has_cov;
+    const int32_t* kf_cov_off;
+    const int32_t* kf_cov;
+} gf_map_delta;
+/* Apply ndelta deltas (any number of streams, each named at most once; every
+ * stream needs a keyframe graph) in one upload and one set of launches, with
+ * no host synchronisation on success. Legal after gf_frontend_capture: no
+ * buffer moves, and the step reads every count it needs from device memory.
+ * Everything is validated on the host first: GF_ERR_ARG for an index out of
+ * range, a row that is not ascending, a duplicate stream / point / slot;
+ * GF_ERR_CAP above 64 keyframes, map_cap points, 64 x keypoint-capacity slots
+ * or observations, or nkf^2 covisibility entries (the capacities do not grow:
+ * a map that outgrows them is the caller's to prune or window);
+ * GF_ERR_UNSUPPORTED for an appended keyframe on a stream with a keyframe
+ * database (gf_frontend_set_kfdb: the database and the graph must agree in
+ * keyframes). A failing delta leaves every stream of the call untouched.
+ * After the call the map's cached copies are current: the float3 positions,
+ * GF_FE_LAST_POS of the last frame's points, the graph's mp_bad. A stream not
+ * named and every row not addressed are byte-identical before and after. */
+int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* deltas);
+/* The keyframe graph the front end holds for a stream. counts[5] = nkf, nmp,
+ * slots, covisibility entries, observations (always written); the arrays of
+ * `out` are caller buffers with caps[3] = slot, covisibility and observation
+ * capacity, and room for 64 + 1 keyframe entries and map_cap + 1 point entries.
+ * out NULL returns the counts only; a cap too small: GF_ERR_CAP, nothing
+ * copied. Synchronises. */
+typedef struct gf_covis_out {
+    uint8_t* kf_bad;
+    int32_t* kf_mp_off;
+    int32_t* kf_mp;
+    int32_t* kf_cov_off;
+    int32_t* kf_cov;
+    uint8_t* mp_bad;
+    int32_t* mp_obs_off;
+    int32_t* mp_obs;
+} gf_covis_out;
+int gf_frontend_get_covis(gf_frontend* fe, int stream, int32_t* counts, const gf_covis_out* out, const int32_t* caps);
+
 /* ------------------------------------- NeedNewKeyFrame / CreateNewKeyFrame
  * `if(NeedNewKeyFrame()) CreateNewKeyFrame();` (Tracking.cc:896-897), the
  * only way a frame becomes a keyframe: a stage of the step between the
