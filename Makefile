@@ -170,6 +170,15 @@ all: $(MAPUPDATEREF)
 $(MAPUPDATEREF): tests/helpers/mapupdate_ref.cpp include/gfslam/abi.h
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of the relocalisation database that grows:
+# KeyFrameDatabase::add into the packed inverted file, the append of database
+# rows and the verdicts (tests/test_kfdb_grow_cpu.py, tests/test_kfdb_grow_gpu.py),
+# same flags
+KFDBREF = tests/helpers/libkfdbref.so
+all: $(KFDBREF)
+$(KFDBREF): tests/helpers/kfdb_ref.cpp include/gfslam/abi.h
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # C++ drop-in layer driver (tests/test_dropin_gpu.py runs it on the GPU box)
 DROPIN = tests/cpp/dropin_frontend
 all: $(DROPIN)

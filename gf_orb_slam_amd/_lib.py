@@ -226,6 +226,9 @@ _PROTOS = {
     "gf_frontend_set_covis": [_P, _I, _P],
     "gf_kfdb_create": [_P, _P, _P],
     "gf_kfdb_destroy": [_P],
+    "gf_kfdb_create_growable": [_P, _P, _I, _I, _P],
+    "gf_kfdb_append": [_P, _P],
+    "gf_kfdb_read": [_P, _P, _P, _P, _P, _P, _P],
     "gf_frontend_set_kfdb": [_P, _I, _P],
     "gf_frontend_set_vocab": [_P, _P],
     "gf_window_search": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P],
@@ -251,6 +254,7 @@ _PROTOS = {
     "gf_frontend_write": [_P, _I, _P, _S],
     "gf_frontend_field": [_P, _I, _P, _P],
     "gf_frontend_update_maps": [_P, _I, _P],
+    "gf_frontend_update_maps_kfdb": [_P, _I, _P, _P],
     "gf_frontend_get_covis": [_P, _I, _P, _P, _P],
     "gf_need_new_keyframe": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "gf_need_new_keyframe_dev": [_P, _P, _P],

@@ -900,6 +900,7 @@ struct gf_frontend {
     gf_vocab* voc = nullptr;
     bool rl_alloc = false, rl_on = false;
     std::vector<gf::KfdbDev> h_kfdb;
+    std::vector<gf_kfdb*> kfdb_obj;  // the attached databases that grow (null: none or a fixed one)
     gf::KfdbDev* d_kfdb = nullptr;
     std::vector<int32_t> h_kfc;
     int32_t* d_kfc = nullptr;
@@ -926,6 +927,13 @@ struct gf_frontend {
     uint8_t* mu_pin[2] = {nullptr, nullptr};
     hipEvent_t mu_ev[2] = {nullptr, nullptr};
     int mu_turn = 0;
+    // the keyframe rows of gf_frontend_update_maps_kfdb: staging of their own,
+    // sized by the largest call so far (pinned buffers in turn with mu_pin;
+    // outgrown ones are kept until the front end goes, so growing never waits)
+    uint8_t* kg_stage = nullptr;
+    uint8_t* kg_pin[2] = {nullptr, nullptr};
+    size_t kg_bytes = 0, kg_pin_bytes[2] = {0, 0};
+    std::vector<void*> kg_old_pins;
 };
 
 namespace {
@@ -965,10 +973,14 @@ void fe_free(gf_frontend* fe) {
     fe->allocs.clear();
     for (int i = 0; i < 2; i++) {
         if (fe->mu_pin[i]) (void)hipHostFree(fe->mu_pin[i]);
+        if (fe->kg_pin[i]) (void)hipHostFree(fe->kg_pin[i]);
+        fe->kg_pin[i] = nullptr;
         if (fe->mu_ev[i]) (void)hipEventDestroy(fe->mu_ev[i]);
         fe->mu_pin[i] = nullptr;
         fe->mu_ev[i] = nullptr;
     }
+    for (void* p : fe->kg_old_pins) (void)hipHostFree(p);
+    fe->kg_old_pins.clear();
     if (fe->ex) (void)gf_extractor_destroy(fe->ex);
     fe->ex = nullptr;
 }
@@ -1420,6 +1432,7 @@ int gf_frontend_create(gf_ctx* ctx, const gf_frontend_params* p, gf_frontend** o
     if (hipMemcpy(fe->d_kfc, fe->h_kfc.data(), 4 * (size_t)B, hipMemcpyHostToDevice) != hipSuccess)
         return bail(gf::fail(GF_ERR_HIP, "upload keyframe counts"));
     fe->h_kfdb.assign(B, gf::KfdbDev{});
+    fe->kfdb_obj.assign(B, nullptr);
     TL.B = B;
     TL.cap = cap;
     TL.M = M;
@@ -1649,8 +1662,14 @@ int gf_frontend_set_covis(gf_frontend* fe, int stream, const gf_covis_map* g) {
     fe->h_nc[b] = (int32_t)nc;
     fe->h_obs_len[b].resize(nmp);
     for (int m = 0; m < nmp; m++) fe->h_obs_len[b][m] = g->mp_obs_off[m + 1] - g->mp_obs_off[m];
-    if (fe->rl_alloc && fe->h_kfdb[b].nkf) FE_RC(gf_frontend_set_kfdb(fe, stream, nullptr));
+    if (fe->rl_alloc && (fe->h_kfdb[b].nkf || fe->kfdb_obj[b])) FE_RC(gf_frontend_set_kfdb(fe, stream, nullptr));
     return GF_OK;
+}
+
+// Some stream has keyframes to relocalise against, or a database that can get some.
+static bool fe_any_kfdb(const gf_frontend* fe) {
+    return std::any_of(fe->h_kfdb.begin(), fe->h_kfdb.end(), [](const gf::KfdbDev& k) { return k.nkf > 0; }) ||
+           std::any_of(fe->kfdb_obj.begin(), fe->kfdb_obj.end(), [](const gf_kfdb* g) { return g != nullptr; });
 }
 
 static int fe_enable_reloc(gf_frontend* fe) {
@@ -1701,8 +1720,11 @@ int gf_frontend_set_kfdb(gf_frontend* fe, int stream, gf_kfdb* db) {
     GF_HIP(hipSetDevice(fe->ctx->device));
     GF_HIP(hipStreamSynchronize(fe->ctx->stream));
     gf::KfdbDev v{};
+    const bool grows = db && gf::kfdb_growable(db);
     if (db) {
         v = gf::kfdb_dev(db);
+        GF_CHECK(!grows || db == fe->kfdb_obj[stream] || !gf::kfdb_bound(db), GF_ERR_ARG,
+                 "a growable keyframe database belongs to one stream of one front end");
         GF_CHECK(fe->covis_set && fe->has_covis[stream], GF_ERR_ARG,
                  "a keyframe database needs the stream's keyframe graph (gf_frontend_set_covis)");
         GF_CHECK(v.nkf == fe->h_kfc[stream], GF_ERR_ARG, "the database and the keyframe graph differ in keyframes");
@@ -1713,15 +1735,24 @@ int gf_frontend_set_kfdb(gf_frontend* fe, int stream, gf_kfdb* db) {
                      "keyframe " + std::to_string(k) + ": keypoints and graph slots differ");
     }
     if (!fe->rl_alloc) FE_RC(fe_enable_reloc(fe));
+    if (fe->kfdb_obj[stream]) gf::kfdb_unbind(fe->kfdb_obj[stream]);
+    fe->kfdb_obj[stream] = nullptr;
+    if (grows) {  // the record as the device holds it (the word count of the inverted file lives there)
+        FE_RC(gf::kfdb_bind(db, &v));
+        fe->kfdb_obj[stream] = db;
+    }
     fe->h_kfdb[stream] = v;
     GF_HIP(hipMemcpy(fe->d_kfdb + stream, &v, sizeof(v), hipMemcpyHostToDevice));
     GF_HIP(hipMemset(fe->TL.rkf + (size_t)stream * gf::RL_NC, 0, sizeof(gf_reloc_kf) * gf::RL_NC));
     GF_HIP(hipMemset(fe->TL.ncand + stream, 0, 4));  // no candidates of an earlier database survive
+    // candidate slots: a database that grows counts its capacity, so that a
+    // captured graph stays valid while it does
     int ncs = 1;
     for (const gf::KfdbDev& k : fe->h_kfdb) ncs = std::max(ncs, k.nkf);
+    for (const gf_kfdb* g : fe->kfdb_obj)
+        if (g) ncs = std::max(ncs, gf::kfdb_max_kf(g));
     fe->TL.ncs = ncs;
-    fe->rl_on = fe->voc && ncs > 0 && std::any_of(fe->h_kfdb.begin(), fe->h_kfdb.end(),
-                                                  [](const gf::KfdbDev& k) { return k.nkf > 0; });
+    fe->rl_on = fe->voc && fe_any_kfdb(fe);
     fe->TL.rl_on = fe->rl_on;
     return GF_OK;
 }
@@ -1735,8 +1766,7 @@ int gf_frontend_set_vocab(gf_frontend* fe, gf_vocab* voc) {
         GF_HIP(hipMemset(fe->TL.ncand, 0, 4 * (size_t)fe->D.B));
     }
     fe->voc = voc;
-    fe->rl_on = fe->voc && std::any_of(fe->h_kfdb.begin(), fe->h_kfdb.end(),
-                                       [](const gf::KfdbDev& k) { return k.nkf > 0; });
+    fe->rl_on = fe->voc && fe_any_kfdb(fe);
     fe->TL.rl_on = fe->rl_on;
     return GF_OK;
 }
@@ -2047,6 +2077,7 @@ inline size_t mu_a16(size_t n) { return (n + 15) & ~(size_t)15; }
 struct MuPlan {
     gf::MuHdr h{};
     std::vector<int32_t> slot_pos, row_of, kf_off;
+    gf::KfdbGrowPlan grow;  // db set: the delta's keyframes join the stream's database
 };
 
 // Staging bytes one stream can need at the capacities (the sections of MuHdr).
@@ -2060,7 +2091,7 @@ size_t mu_stream_cap_bytes(size_t M, size_t slot_cap, size_t KC) {
            + mu_a16(4 * (KC + 1)) + mu_a16(4 * KC * KC);                // covisibility
 }
 
-int mu_validate(gf_frontend* fe, const gf_map_delta& d, MuPlan& P) {
+int mu_validate(gf_frontend* fe, const gf_map_delta& d, const gf_keyframe_db* rows, MuPlan& P) {
     const int b = d.stream, M = fe->D.M, KC = gf_frontend::KF_CAP;
     const std::string at = "stream " + std::to_string(b) + ": ";
     GF_CHECK(fe->has_covis[b], GF_ERR_ARG, at + "no keyframe graph (gf_frontend_set_covis)");
@@ -2080,8 +2111,19 @@ int mu_validate(gf_frontend* fe, const gf_map_delta& d, MuPlan& P) {
     GF_CHECK((long long)h.nkf0 + d.n_new_kf <= KC, GF_ERR_CAP, at + "more than 64 keyframes");
     h.nmp1 = h.nmp0 + d.n_new_mp;
     h.nkf1 = h.nkf0 + d.n_new_kf;
-    GF_CHECK(!(d.n_new_kf && fe->rl_alloc && fe->h_kfdb[b].nkf), GF_ERR_UNSUPPORTED,
-             at + "a keyframe database is attached: it cannot grow with the graph (detach it first)");
+    {
+        gf_kfdb* grows = fe->rl_alloc ? fe->kfdb_obj[b] : nullptr;
+        const bool has_db = fe->rl_alloc && (fe->h_kfdb[b].nkf || grows);
+        GF_CHECK(!rows || (has_db && d.n_new_kf), GF_ERR_ARG,
+                 at + "keyframe rows without a keyframe database or without an appended keyframe");
+        GF_CHECK(!(d.n_new_kf && has_db) || (grows && rows), GF_ERR_UNSUPPORTED,
+                 at + "a keyframe database is attached: an appended keyframe needs a database that grows "
+                      "(gf_kfdb_create_growable) and its rows (gf_frontend_update_maps_kfdb)");
+        if (rows) {
+            GF_CHECK(rows->nkf == d.n_new_kf, GF_ERR_ARG, at + "the rows and the delta differ in appended keyframes");
+            FE_RC(gf::kfdb_grow_validate(grows, rows, P.grow));
+        }
+    }
     std::vector<uint8_t> mark((size_t)std::max(h.nmp1, 1), 0);
     h.n_set = d.n_set_mp;
     for (int i = 0; i < d.n_set_mp; i++) {
@@ -2109,6 +2151,9 @@ int mu_validate(gf_frontend* fe, const gf_map_delta& d, MuPlan& P) {
             GF_CHECK(d.new_kf_off[k] <= d.new_kf_off[k + 1], GF_ERR_ARG, at + "keyframe offsets must be ascending");
         nnew = d.new_kf_off[d.n_new_kf];
         GF_CHECK(nnew == 0 || d.new_kf_mp, GF_ERR_ARG, at + "null slot array");
+        for (int k = 0; rows && k < d.n_new_kf; k++)
+            GF_CHECK(rows->kp_off[k + 1] - rows->kp_off[k] == d.new_kf_off[k + 1] - d.new_kf_off[k], GF_ERR_ARG,
+                     at + "appended keyframe " + std::to_string(k) + ": keypoints and graph slots differ");
     }
     GF_CHECK(ns0 + nnew <= (long long)fe->slot_cap, GF_ERR_CAP, at + "more keyframe slots than the capacity");
     h.ns1 = (int32_t)(ns0 + nnew);
@@ -2196,7 +2241,33 @@ int mu_alloc(gf_frontend* fe) {
 
 }  // namespace
 
+// The staging of the call's keyframe rows: device buffer and this turn's pinned
+// buffer at `bytes` at least.
+static int kg_alloc(gf_frontend* fe, int turn, size_t bytes) {
+    if (bytes > fe->kg_bytes) {
+        const size_t n = std::max(bytes, 2 * fe->kg_bytes);
+        void* p = nullptr;
+        FE_RC(fe_alloc(fe, n, &p));
+        fe->kg_stage = (uint8_t*)p;
+        fe->kg_bytes = n;
+    }
+    if (bytes > fe->kg_pin_bytes[turn]) {
+        const size_t n = std::max(bytes, 2 * fe->kg_pin_bytes[turn]);
+        uint8_t* p = nullptr;
+        GF_HIP(hipHostMalloc((void**)&p, n, hipHostMallocDefault));
+        if (fe->kg_pin[turn]) fe->kg_old_pins.push_back(fe->kg_pin[turn]);
+        fe->kg_pin[turn] = p;
+        fe->kg_pin_bytes[turn] = n;
+    }
+    return GF_OK;
+}
+
 int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* deltas) {
+    return gf_frontend_update_maps_kfdb(fe, ndelta, deltas, nullptr);
+}
+
+int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta* deltas,
+                                 const gf_keyframe_db* const* kf_rows) {
     GF_CHECK(fe && ndelta >= 0 && (ndelta == 0 || deltas), GF_ERR_ARG, "bad arguments");
     if (ndelta == 0) return GF_OK;
     GF_CHECK(fe->covis_set, GF_ERR_ARG, "map feedback needs keyframe graphs (gf_frontend_set_covis)");
@@ -2220,11 +2291,22 @@ int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* del
     }
     // validate every delta before anything is written
     std::vector<MuPlan> plans(ndelta);
-    for (int i = 0; i < ndelta; i++) FE_RC(mu_validate(fe, deltas[i], plans[i]));
+    for (int i = 0; i < ndelta; i++) FE_RC(mu_validate(fe, deltas[i], kf_rows ? kf_rows[i] : nullptr, plans[i]));
     FE_RC(mu_alloc(fe));
     // pack: headers, then every stream's sections
     const int turn = fe->mu_turn;
     GF_HIP(hipEventSynchronize(fe->mu_ev[turn]));  // the upload that last used this buffer (two calls ago)
+    int ngrow = 0;
+    size_t kg_need = 0;
+    for (const MuPlan& P : plans)
+        if (P.grow.db) {
+            ngrow++;
+            kg_need += gf::kfdb_grow_bytes(P.grow);
+        }
+    if (ngrow) {
+        kg_need += gf::kfdb_grow_hdr_bytes(ngrow);
+        FE_RC(kg_alloc(fe, turn, kg_need));
+    }
     uint8_t* pin = fe->mu_pin[turn];
     size_t at = mu_a16(sizeof(gf::MuHdr) * (size_t)ndelta);
     auto put = [&](const void* src, size_t bytes, size_t room) -> int64_t {
@@ -2286,7 +2368,18 @@ int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* del
         fe->h_obs_len[b].resize(h.nmp1, 0);
         for (int r = 0; r < d.n_obs_rows; r++) fe->h_obs_len[b][d.obs_mp[r]] = d.obs_off[r + 1] - d.obs_off[r];
     }
+    // the appended keyframes' database rows, and the databases' host counts
+    gf::KfdbGrowShape gsh;
+    size_t gat = gf::kfdb_grow_hdr_bytes(ngrow);
+    for (int i = 0, j = 0; i < ndelta && ngrow; i++) {
+        if (!plans[i].grow.db) continue;
+        const int b = plans[i].h.stream;
+        gf::kfdb_grow_pack(plans[i].grow, fe->kg_pin[turn], j++, gat, fe->d_kfdb + b,
+                           fe->TL.rkf + (size_t)b * gf::RL_NC, gsh);
+        fe->h_kfdb[b] = gf::kfdb_dev(plans[i].grow.db);
+    }
     GF_HIP(hipMemcpyAsync(fe->mu_stage, pin, at, hipMemcpyHostToDevice, s));
+    if (ngrow) GF_HIP(hipMemcpyAsync(fe->kg_stage, fe->kg_pin[turn], gat, hipMemcpyHostToDevice, s));
     GF_HIP(hipEventRecord(fe->mu_ev[turn], s));
     fe->mu_turn = turn ^ 1;
     FeDev& D = fe->D;
@@ -2318,7 +2411,8 @@ int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* del
     A.last_pos = D.last_pos;
     A.obs_off_new = fe->mu_off_new;
     A.obs_new = fe->mu_obs_new;
-    return gf::map_update_launch(fe->ctx, A, sh, s);
+    FE_RC(gf::map_update_launch(fe->ctx, A, sh, s));
+    return ngrow ? gf::kfdb_grow_launch(fe->ctx, fe->kg_stage, ngrow, gsh, s) : GF_OK;
 }
 
 int gf_frontend_get_covis(gf_frontend* fe, int stream, int32_t* counts, const gf_covis_out* out, const int32_t* caps) {

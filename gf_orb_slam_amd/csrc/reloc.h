@@ -3,6 +3,8 @@
 // frontend.hip fills a TrackLossArgs once per front end and launches the two
 // stages inside its step.
 #pragma once
+#include <vector>
+
 #include "common.h"
 #include "match_common.h"
 
@@ -115,6 +117,43 @@ struct TrackLossArgs {
 
 // The device arrays of a keyframe database (gf_kfdb_create).
 const KfdbDev& kfdb_dev(const gf_kfdb* db);
+// The checks of gf_kfdb_create on a database's arrays -> its keypoints, BowVector
+// entries, FeatureVector nodes and features (GF_ERR_ARG otherwise).
+int kfdb_validate(const gf_keyframe_db* db, int& nk, int& nb, int& nn, int& nf);
+
+// ---- a database that grows (kfdbgrow.hip)
+// One validated append: the rows' sizes and the delta inverted file of the new
+// keyframes (their words merged: u ascending, word u's new keyframes at
+// ukf[uoff[u] .. uoff[u + 1]) in index order).
+struct KfdbGrowPlan {
+    gf_kfdb* db = nullptr;
+    const gf_keyframe_db* rows = nullptr;
+    int nk = 0, nb = 0, nn = 0, nf = 0;
+    std::vector<int32_t> u, uoff, ukf;
+};
+// Largest per-database counts of a call, for the grids.
+struct KfdbGrowShape {
+    int work = 0;
+};
+bool kfdb_growable(const gf_kfdb* db);
+int kfdb_max_kf(const gf_kfdb* db);
+bool kfdb_bound(const gf_kfdb* db);
+// Binds a growable database to its one stream (GF_ERR_ARG when it is bound) and
+// releases it; the record as the device holds it now (synchronous).
+int kfdb_bind(gf_kfdb* db, KfdbDev* rec);
+void kfdb_unbind(gf_kfdb* db);
+// gf_kfdb_create's checks on `rows` (offsets from 0) and the database's
+// capacities: GF_ERR_ARG / GF_ERR_CAP, the database untouched.
+int kfdb_grow_validate(gf_kfdb* db, const gf_keyframe_db* rows, KfdbGrowPlan& P);
+size_t kfdb_grow_hdr_bytes(int ndb);
+size_t kfdb_grow_bytes(const KfdbGrowPlan& P);
+// Packs database `i` of a call into the staging image `pin` (its header at
+// slot i, its sections from `at`, which advances) and advances the database's
+// host counts. fe_rec: the front end's record of the stream (device) and rkf
+// its keyframes' query state, or null.
+void kfdb_grow_pack(const KfdbGrowPlan& P, uint8_t* pin, int i, size_t& at, KfdbDev* fe_rec, gf_reloc_kf* rkf,
+                    KfdbGrowShape& sh);
+int kfdb_grow_launch(gf_ctx* ctx, const uint8_t* stage, int ndb, const KfdbGrowShape& sh, hipStream_t s);
 
 // DetectRelocalisationCandidates for the streams that relocalise and their
 // SearchByBoW pairs (k_match_bow then runs over A.pairs).
@@ -124,3 +163,23 @@ int reloc_candidates(gf_ctx* ctx, const TrackLossArgs& A, hipStream_t s);
 int track_loss(gf_ctx* ctx, const TrackLossArgs& A, hipStream_t s);
 
 }  // namespace gf
+
+struct gf_kfdb {
+    int device = 0;  // the context's device (the context may go first)
+    gf::KfdbDev dev{};
+    std::vector<void*> allocs;
+    // gf_kfdb_create_growable: arrays at the capacities, two inverted files
+    // written in turn, the record in device memory (d_rec: what the kernels
+    // read and flip; dev follows it on the host but for nw, which only the
+    // device knows), and the host's counts
+    bool growable = false, bound = false;
+    gf_ctx* ctx = nullptr;
+    int max_kf = 0, max_rows = 0;
+    int nk = 0, nb = 0, nn = 0, nf = 0;  // keypoints, BowVector entries, FeatureVector nodes and features
+    int side = 0;                        // the inverted file in use
+    int32_t *inv_words[2] = {}, *inv_off[2] = {}, *inv_kf[2] = {};
+    int32_t *scan = nullptr, *pos = nullptr;  // [max_rows + 1], [max_rows] of the merge
+    gf::KfdbDev* d_rec = nullptr;
+    uint8_t* stage = nullptr;  // gf_kfdb_append's staging
+    size_t stage_bytes = 0;
+};

@@ -33,12 +33,6 @@
 #include "reloc.h"
 #include "top2.h"
 
-struct gf_kfdb {
-    int device = 0;  // the context's device (the context may go first)
-    gf::KfdbDev dev{};
-    std::vector<void*> allocs;
-};
-
 namespace {
 
 constexpr int TL_T = 64;  // one wave per stream
@@ -1116,29 +1110,9 @@ int gf_kfdb_create(gf_ctx* ctx, const gf_keyframe_db* db, gf_kfdb** out) {
     GF_CHECK(ctx && db && out, GF_ERR_ARG, "null arg");
     const int nkf = db->nkf;
     GF_CHECK(nkf >= 0 && nkf <= gf::RL_NC, GF_ERR_UNSUPPORTED, "at most 64 keyframes per database");
-    GF_CHECK(nkf == 0 || (db->kp_off && db->bow_off && db->fv_off && db->fv_start), GF_ERR_ARG, "null offsets");
-    const int nk = nkf ? db->kp_off[nkf] : 0, nb = nkf ? db->bow_off[nkf] : 0, nn = nkf ? db->fv_off[nkf] : 0;
-    const int nf = nkf ? db->fv_start[nn] : 0;
-    GF_CHECK(nk >= 0 && nb >= 0 && nn >= 0 && nf >= 0, GF_ERR_ARG, "negative sizes");
-    GF_CHECK((nk == 0 || (db->kps && db->desc)) && (nb == 0 || (db->bow_words && db->bow_values)) &&
-                 (nn == 0 || db->fv_nodes) && (nf == 0 || db->fv_feats),
-             GF_ERR_ARG, "null database arrays");
-    for (int k = 0; k < nkf; k++) {
-        GF_CHECK(db->kp_off[k] >= 0 && db->kp_off[k] <= db->kp_off[k + 1] && db->kp_off[k + 1] - db->kp_off[k] <= KP_MAX,
-                 GF_ERR_ARG, "keypoint offsets must ascend (<= 4096 a keyframe)");
-        GF_CHECK(db->bow_off[k] >= 0 && db->bow_off[k] <= db->bow_off[k + 1], GF_ERR_ARG, "BowVector offsets");
-        GF_CHECK(db->fv_off[k] >= 0 && db->fv_off[k] <= db->fv_off[k + 1], GF_ERR_ARG, "FeatureVector offsets");
-        for (int e = db->bow_off[k] + 1; e < db->bow_off[k + 1]; e++)
-            GF_CHECK(db->bow_words[e] > db->bow_words[e - 1], GF_ERR_ARG, "BowVector words must ascend");
-        const int nkp = db->kp_off[k + 1] - db->kp_off[k];
-        for (int g = db->fv_off[k]; g < db->fv_off[k + 1]; g++) {
-            GF_CHECK(db->fv_start[g] >= 0 && db->fv_start[g] <= db->fv_start[g + 1] && db->fv_start[g + 1] <= nf,
-                     GF_ERR_ARG, "FeatureVector starts must ascend");
-            if (g > db->fv_off[k]) GF_CHECK(db->fv_nodes[g] > db->fv_nodes[g - 1], GF_ERR_ARG, "nodes must ascend");
-            for (int x = db->fv_start[g]; x < db->fv_start[g + 1]; x++)
-                GF_CHECK(db->fv_feats[x] >= 0 && db->fv_feats[x] < nkp, GF_ERR_ARG, "feature index out of range");
-        }
-    }
+    int nk, nb, nn, nf;
+    const int vrc = gf::kfdb_validate(db, nk, nb, nn, nf);
+    if (vrc) return vrc;
     GF_HIP(hipSetDevice(ctx->device));
     gf_kfdb* d = new gf_kfdb();
     d->device = ctx->device;
@@ -1237,3 +1211,31 @@ int gf_reloc_candidates(gf_ctx* ctx, const int32_t* words, const double* values,
 }  // extern "C"
 
 const gf::KfdbDev& gf::kfdb_dev(const gf_kfdb* db) { return db->dev; }
+
+int gf::kfdb_validate(const gf_keyframe_db* db, int& nk, int& nb, int& nn, int& nf) {
+    const int nkf = db->nkf;
+    GF_CHECK(nkf == 0 || (db->kp_off && db->bow_off && db->fv_off && db->fv_start), GF_ERR_ARG, "null offsets");
+    nk = nkf ? db->kp_off[nkf] : 0, nb = nkf ? db->bow_off[nkf] : 0, nn = nkf ? db->fv_off[nkf] : 0;
+    nf = nkf ? db->fv_start[nn] : 0;
+    GF_CHECK(nk >= 0 && nb >= 0 && nn >= 0 && nf >= 0, GF_ERR_ARG, "negative sizes");
+    GF_CHECK((nk == 0 || (db->kps && db->desc)) && (nb == 0 || (db->bow_words && db->bow_values)) &&
+                 (nn == 0 || db->fv_nodes) && (nf == 0 || db->fv_feats),
+             GF_ERR_ARG, "null database arrays");
+    for (int k = 0; k < nkf; k++) {
+        GF_CHECK(db->kp_off[k] >= 0 && db->kp_off[k] <= db->kp_off[k + 1] && db->kp_off[k + 1] - db->kp_off[k] <= KP_MAX,
+                 GF_ERR_ARG, "keypoint offsets must ascend (<= 4096 a keyframe)");
+        GF_CHECK(db->bow_off[k] >= 0 && db->bow_off[k] <= db->bow_off[k + 1], GF_ERR_ARG, "BowVector offsets");
+        GF_CHECK(db->fv_off[k] >= 0 && db->fv_off[k] <= db->fv_off[k + 1], GF_ERR_ARG, "FeatureVector offsets");
+        for (int e = db->bow_off[k] + 1; e < db->bow_off[k + 1]; e++)
+            GF_CHECK(db->bow_words[e] > db->bow_words[e - 1], GF_ERR_ARG, "BowVector words must ascend");
+        const int nkp = db->kp_off[k + 1] - db->kp_off[k];
+        for (int g = db->fv_off[k]; g < db->fv_off[k + 1]; g++) {
+            GF_CHECK(db->fv_start[g] >= 0 && db->fv_start[g] <= db->fv_start[g + 1] && db->fv_start[g + 1] <= nf,
+                     GF_ERR_ARG, "FeatureVector starts must ascend");
+            if (g > db->fv_off[k]) GF_CHECK(db->fv_nodes[g] > db->fv_nodes[g - 1], GF_ERR_ARG, "nodes must ascend");
+            for (int x = db->fv_start[g]; x < db->fv_start[g + 1]; x++)
+                GF_CHECK(db->fv_feats[x] >= 0 && db->fv_feats[x] < nkp, GF_ERR_ARG, "feature index out of range");
+        }
+    }
+    return GF_OK;
+}

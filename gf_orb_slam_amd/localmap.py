@@ -74,11 +74,15 @@ class MapDelta:
     slot_kf / slot_idx / slot_val: slot writes on existing keyframes; obs_rows:
     {point: ascending observing keyframes}, the whole new row of every touched
     point; kf_cov: a list of the ordered covisible keyframes of every keyframe
-    (old and appended), or None when the lists are unchanged."""
+    (old and appended), or None when the lists are unchanged; kf_rows: the
+    appended keyframes' relocalisation database rows, for a stream whose
+    database grows: a pipeline.KeyframeDB of them (offsets from 0) or a list of
+    (kps, desc, words, values, FeatureVector), one per appended keyframe; None:
+    the delta carries none."""
 
     def __init__(self, stream: int, new_mp=None, new_mp_desc=None, new_mp_bad=None, set_mp_idx=None, set_mp=None,
                  set_mp_desc=None, bad_mp=None, new_kf=None, new_kf_bad=None, bad_kf=None, slot_kf=None, slot_idx=None,
-                 slot_val=None, obs_rows=None, kf_cov=None):
+                 slot_val=None, obs_rows=None, kf_cov=None, kf_rows=None):
         from .matcher import MAP_POINT_DTYPE
 
         def arr(a, dt, shape=(-1,)):
@@ -113,6 +117,12 @@ class MapDelta:
         self.kf_cov_off = np.zeros(len(crow) + 1, np.int32)
         self.kf_cov_off[1:] = np.cumsum([len(c) for c in crow])
         self.kf_cov = arr(np.concatenate(crow) if crow else None, np.int32)
+        if kf_rows is not None and not hasattr(kf_rows, "struct"):
+            from .pipeline import KeyframeDB
+
+            it = iter([(r[2], r[3], r[4]) for r in kf_rows])
+            kf_rows = KeyframeDB([r[0] for r in kf_rows], [r[1] for r in kf_rows], lambda d: next(it))
+        self.kf_rows = kf_rows
         if not (len(self.new_mp) == len(self.new_mp_desc) == len(self.new_mp_bad) and
                 len(self.set_mp_idx) == len(self.set_mp) == len(self.set_mp_desc) and
                 len(self.slot_kf) == len(self.slot_idx) == len(self.slot_val) and len(self.new_kf_bad) == len(rows)):

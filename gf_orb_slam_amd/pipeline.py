@@ -348,11 +348,14 @@ class FrontEnd:
         self._graphs = getattr(self, "_graphs", {})
         self._graphs[stream] = g
         check(lib().gf_frontend_set_covis(self.handle, stream, ctypes.byref(g.struct())))
+        getattr(self, "_kfdbs", {}).pop(stream, None)  # a database set earlier indexed the old graph: detached
 
     def update_maps(self, deltas) -> None:
         """gf_frontend_update_maps: apply the mapper's changes (a
         localmap.MapDelta or a list of them, one per stream at most) to the
-        stream maps and keyframe graphs in place, behind the last step, without
+        stream maps and keyframe graphs in place (and, for the deltas that
+        carry ``kf_rows``, the appended keyframes to the stream's growable
+        KeyframeDB, whose host arrays follow), behind the last step, without
         a host synchronisation; legal after capture_graph(). A refused delta
         (GFError) leaves every stream of the call untouched."""
         from .localmap import MapDelta, MapDeltaStruct
@@ -361,7 +364,17 @@ class FrontEnd:
         if not ds:
             return
         arr = (MapDeltaStruct * len(ds))(*[d.struct() for d in ds])
-        check(lib().gf_frontend_update_maps(self.handle, len(ds), arr))
+        if all(d.kf_rows is None for d in ds):
+            check(lib().gf_frontend_update_maps(self.handle, len(ds), arr))
+            return
+        # the appended keyframes' database rows travel with their deltas (gf_frontend_update_maps_kfdb)
+        rows = [d.kf_rows.struct() if d.kf_rows is not None else None for d in ds]
+        ptrs = (ctypes.c_void_p * len(ds))(*[ctypes.addressof(r) if r is not None else None for r in rows])
+        check(lib().gf_frontend_update_maps_kfdb(self.handle, len(ds), arr, ptrs))
+        for d in ds:  # the host arrays follow the device
+            db = getattr(self, "_kfdbs", {}).get(d.stream)
+            if d.kf_rows is not None and db is not None:
+                db.extend(d.kf_rows)
 
     def covis(self, stream: int) -> dict:
         """gf_frontend_get_covis: the keyframe graph the front end holds for
@@ -392,8 +405,8 @@ class FrontEnd:
         """gf_frontend_set_kfdb: the stream's keyframe database (a
         KeyframeDB over the same keyframes as its graph; None detaches)."""
         self._kfdbs = getattr(self, "_kfdbs", {})
-        self._kfdbs[stream] = db
         check(lib().gf_frontend_set_kfdb(self.handle, stream, db.device(self.ctx) if db is not None else None))
+        self._kfdbs[stream] = db
 
     def bootstrap(self, Tcw: np.ndarray, V: np.ndarray, t0: float = 0.0) -> None:
         T = np.ascontiguousarray(Tcw, np.float32).reshape(self.B, 16)
@@ -610,11 +623,23 @@ class KeyframeDB:
     gf_keyframe_db): per keyframe its keypoints, descriptors, BowVector and
     FeatureVector (KeyFrame::ComputeBoW, levelsup 4). `transform(desc)` gives
     (words, values, FeatureVector) — the library's ORBVocabulary.transform on
-    the device, or a CPU restatement in the oracle tests."""
+    the device, or a CPU restatement in the oracle tests.
 
-    def __init__(self, kf_kps: list, kf_desc: list, transform):
+    With ``max_kf`` and ``max_rows`` the device database grows
+    (gf_kfdb_create_growable: room for max_kf keyframes and max_rows keypoints
+    in total): ``append`` adds a keyframe, and a ``FrontEnd`` it is attached to
+    adds the keyframes of the map deltas that carry their rows. It then belongs
+    to that one stream. Without them it is fixed and can be shared."""
+
+    _ARRAYS = ("kp_off", "kps", "desc", "bow_off", "bow_words", "bow_values", "fv_off", "fv_nodes", "fv_start",
+               "fv_feats")
+
+    def __init__(self, kf_kps: list, kf_desc: list, transform, max_kf=None, max_rows=None):
         from .orb import KEYPOINT_DTYPE
 
+        if (max_kf is None) != (max_rows is None):
+            raise ValueError("a growable database needs both max_kf and max_rows")
+        self.max_kf, self.max_rows = max_kf, max_rows
         self.nkf = len(kf_kps)
         kps = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k in kf_kps]
         desc = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in kf_desc]
@@ -640,20 +665,107 @@ class KeyframeDB:
         self.fv_nodes, self.fv_feats = cat(fn, np.int32), cat(ff, np.int32)
         self.fv_start = np.ascontiguousarray(fs, np.int32)
         self._dev = {}
+        self._buf = None
+        if self.growable:
+            self.reserve()
+
+    @property
+    def growable(self) -> bool:
+        return self.max_kf is not None
+
+    def reserve(self) -> None:
+        """Host arrays of a growable database at its capacities (the arrays
+        become views of them), so that ``extend`` costs the new rows only."""
+        K, R = int(self.max_kf), int(self.max_rows)
+        cap = dict(kp_off=K + 1, kps=R, desc=R, bow_off=K + 1, bow_words=R, bow_values=R, fv_off=K + 1, fv_nodes=R,
+                   fv_start=R + 1, fv_feats=R)
+        self._buf = {}
+        for k, n in cap.items():
+            a = getattr(self, k)
+            b = np.zeros((max(n, len(a)),) + a.shape[1:], a.dtype)
+            b[:len(a)] = a
+            self._buf[k] = b
+            setattr(self, k, b[:len(a)])
+
+    @classmethod
+    def rows(cls, kps, desc, words, values, fv) -> "KeyframeDB":
+        """One keyframe's rows (offsets from 0), as ``append`` and a
+        ``MapDelta`` carry them."""
+        return cls([kps], [desc], lambda d: (words, values, fv))
 
     def struct(self) -> KeyframeDBArrays:
-        a = [self.kp_off, self.kps, self.desc, self.bow_off, self.bow_words, self.bow_values, self.fv_off,
-             self.fv_nodes, self.fv_start, self.fv_feats]
+        a = [getattr(self, k) for k in self._ARRAYS]
         return KeyframeDBArrays(self.nkf, *[x.ctypes.data if x.size else None for x in a])
 
     def device(self, ctx):
-        """The gf_kfdb handle on ctx (created once, shared by the streams)."""
+        """The gf_kfdb handle on ctx (created once; a fixed one is shared by
+        the streams)."""
         key = id(ctx)
         if key not in self._dev:
             h = ctypes.c_void_p()
-            check(lib().gf_kfdb_create(ctx.handle, ctypes.byref(self.struct()), ctypes.byref(h)))
+            if self.growable:
+                if self._dev:
+                    raise ValueError("a growable database lives on one context")
+                check(lib().gf_kfdb_create_growable(ctx.handle, ctypes.byref(self.struct()), self.max_kf,
+                                                    self.max_rows, ctypes.byref(h)))
+            else:
+                check(lib().gf_kfdb_create(ctx.handle, ctypes.byref(self.struct()), ctypes.byref(h)))
             self._dev[key] = (ctx, h)  # the context outlives the handle
         return self._dev[key][1]
+
+    def extend(self, rows: "KeyframeDB") -> None:
+        """The host arrays with the keyframes of ``rows`` behind them (what the
+        device holds after a successful append)."""
+        base = dict(kp_off=self.kp_off[-1], bow_off=self.bow_off[-1], fv_off=self.fv_off[-1], fv_start=self.fv_start[-1])
+        for k in self._ARRAYS:
+            cur, new = getattr(self, k), getattr(rows, k)
+            new = new[1:] + base[k] if k in base else new
+            n0, n1 = len(cur), len(cur) + len(new)
+            if self._buf is not None and n1 <= len(self._buf[k]):  # in place, behind the used part
+                self._buf[k][n0:n1] = new
+                setattr(self, k, self._buf[k][:n1])
+            else:
+                self._buf = None
+                setattr(self, k, np.ascontiguousarray(np.concatenate([cur, new]), cur.dtype))
+        self.nkf += rows.nkf
+
+    def append(self, kps, desc=None, words=None, values=None, fv=None) -> None:
+        """gf_kfdb_append: one more keyframe (index nkf) with its BowVector
+        and FeatureVector, or the keyframes of a KeyframeDB of rows given as
+        ``kps``. Synchronous; a database attached to a front end gets its
+        keyframes through ``FrontEnd.update_maps`` instead."""
+        from ._lib import GFError
+
+        rows = kps if isinstance(kps, KeyframeDB) else KeyframeDB.rows(kps, desc, words, values, fv)
+        if not self._dev and not self.growable:
+            raise GFError(-1, "the keyframe database is fixed")
+        for _, h in self._dev.values():
+            check(lib().gf_kfdb_append(h, ctypes.byref(rows.struct())))
+        self.extend(rows)
+
+    def read(self, ctx) -> dict:
+        """gf_kfdb_read: the device database and its inverted file, packed:
+        the arrays of gf_keyframe_db plus inv_words / inv_off / inv_kf."""
+        from .orb import KEYPOINT_DTYPE
+
+        h = self.device(ctx)
+        counts = np.zeros(6, np.int32)
+        check(lib().gf_kfdb_read(h, ptr(counts), None, None, None, None, None))
+        nkf, nk, nb, nn, nf, nw = (int(c) for c in counts)
+        shape = dict(kp_off=(nkf + 1, np.int32), kps=(nk, KEYPOINT_DTYPE), desc=((nk, 32), np.uint8),
+                     bow_off=(nkf + 1, np.int32), bow_words=(nb, np.int32), bow_values=(nb, np.float64),
+                     fv_off=(nkf + 1, np.int32), fv_nodes=(nn, np.int32), fv_start=(nn + 1, np.int32),
+                     fv_feats=(nf, np.int32), inv_words=(nw, np.int32), inv_off=(nw + 1, np.int32),
+                     inv_kf=(nb, np.int32))
+        size = lambda sh: int(np.prod(sh))  # noqa: E731
+        buf = {k: np.zeros(max(size(sh), 1), dt) for k, (sh, dt) in shape.items()}
+        out = KeyframeDBArrays(nkf, *[buf[k].ctypes.data for k in self._ARRAYS])
+        caps = np.array([nkf, nk, nb, nn, nf, nw], np.int32)
+        check(lib().gf_kfdb_read(h, ptr(counts), ctypes.byref(out), ptr(buf["inv_words"]), ptr(buf["inv_off"]),
+                                 ptr(buf["inv_kf"]), ptr(caps)))
+        res = {k: buf[k][:size(sh)].reshape(sh).copy() for k, (sh, dt) in shape.items()}
+        res["nkf"] = nkf
+        return res
 
     def __del__(self):
         try:

@@ -523,7 +523,9 @@ class MapFeedback:
     holds for the stream (points, descriptors, bad flags, slot rows,
     observation rows, covisibility lists), ``delta()`` the difference between
     the ``LoopMap`` and the shadow as a ``localmap.MapDelta``, ``commit()``
-    the shadow advanced after the update succeeded.
+    the shadow advanced after the update succeeded. When the stream has a
+    growable ``KeyframeDB``, the delta carries the new keyframes' database rows
+    (``kf_kps`` / ``kf_desc`` / ``kf_bow`` / ``kf_fv`` of the LoopMap).
 
     The id mapping is the identity: the LoopMap's point id is the map index,
     its keyframe index the graph index, and both only grow. Anything else (a
@@ -578,11 +580,19 @@ class MapFeedback:
         same_cov = (np.array_equal(g1["kf_cov_off"][:k0 + 1], g0["kf_cov_off"]) and
                     np.array_equal(g1["kf_cov"], g0["kf_cov"]) and int(g1["kf_cov_off"][k1]) == len(g0["kf_cov"]))
         co = g1["kf_cov_off"]
+        # a stream whose database grows: the new keyframes join it with the graph (KeyFrameDatabase::add)
+        db = getattr(self.fe, "_kfdbs", {}).get(self.stream)
+        kf_rows = None
+        if k1 > k0 and db is not None and db.growable:
+            for k in range(k0, k1):
+                if m.kf_bow[k] is None or m.kf_fv[k] is None:
+                    raise ValueError(f"keyframe {k} has no BoW yet: it cannot join the keyframe database")
+            kf_rows = [(m.kf_kps[k], m.kf_desc[k], m.kf_bow[k][0], m.kf_bow[k][1], m.kf_fv[k]) for k in range(k0, k1)]
         d = MapDelta(self.stream, new_mp=mp1[n0:], new_mp_desc=desc1[n0:], new_mp_bad=g1["mp_bad"][n0:],
                      set_mp_idx=ch, set_mp=mp1[ch], set_mp_desc=desc1[ch], bad_mp=bad_mp,
                      new_kf=[np.asarray(s, np.int32) for s in m.slots[k0:]], new_kf_bad=g1["kf_bad"][k0:],
                      bad_kf=bad_kf, slot_kf=skf, slot_idx=pos - g0["kf_mp_off"][skf], slot_val=g1["kf_mp"][pos],
-                     obs_rows=obs_rows,
+                     obs_rows=obs_rows, kf_rows=kf_rows,
                      kf_cov=None if same_cov else [g1["kf_cov"][co[k]:co[k + 1]] for k in range(k1)])
         self._next = dict(mp=mp1.copy(), desc=desc1.copy(), graph=g1)
         return d

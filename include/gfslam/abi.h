@@ -1939,8 +1939,43 @@ typedef struct gf_keyframe_db {
 typedef struct gf_kfdb gf_kfdb;
 int gf_kfdb_create(gf_ctx* ctx, const gf_keyframe_db* db, gf_kfdb** out);
 int gf_kfdb_destroy(gf_kfdb* db);
+/* A database that grows with the map (KeyFrameDatabase::add for the keyframes
+ * LocalMapping hands on): the same input as gf_kfdb_create (offsets from 0),
+ * with every device array allocated for max_kf keyframes (<= 64) and max_rows
+ * keypoints in total. A keyframe has at most one BowVector word, one
+ * FeatureVector node and one inverted-file entry per keypoint, so max_rows
+ * bounds those arrays too. The inverted file is kept current on the device. A
+ * database from gf_kfdb_create stays fixed and can be shared between streams;
+ * a growable one belongs to one stream of one front end (attaching it while it
+ * is attached elsewhere: GF_ERR_ARG; gf_frontend_set_kfdb(fe, stream, NULL)
+ * releases it). `ctx` outlives the database's appends. */
+int gf_kfdb_create_growable(gf_ctx* ctx, const gf_keyframe_db* db, int max_kf, int max_rows, gf_kfdb** out);
+/* Host family, synchronous: rows->nkf keyframes (rows' own offsets from 0)
+ * become the keyframes nkf .. nkf + rows->nkf - 1; several in one call give
+ * what appending them one at a time gives. gf_kfdb_create's validation on the
+ * host before anything is enqueued (GF_ERR_ARG: words or nodes not ascending,
+ * a feature index out of range, more words / nodes / features than
+ * keypoints); GF_ERR_CAP above max_kf or max_rows; GF_ERR_ARG on a fixed
+ * database and on one attached to a front end (there the keyframes arrive
+ * with gf_frontend_update_maps_kfdb). A refused call leaves the database
+ * untouched. */
+int gf_kfdb_append(gf_kfdb* db, const gf_keyframe_db* rows);
+/* A database (fixed or growable) and its inverted file read back, packed:
+ * counts[6] = keyframes, keypoints, BowVector entries, FeatureVector nodes,
+ * FeatureVector features, inverted-file words (always written). out NULL
+ * returns the counts only. Otherwise the arrays of `out` are caller buffers
+ * that are written (the struct is the input one, hence its const), inv_words
+ * [words], inv_off [words + 1] and inv_kf [BowVector entries] receive the
+ * inverted file, and caps[6] holds the buffers' capacities in the order of
+ * counts (offset arrays hold one more); a cap too small: GF_ERR_CAP, nothing
+ * copied. Synchronises the device. What a test compares and what a caller
+ * checkpoints: the output is gf_kfdb_create_growable's input. */
+int gf_kfdb_read(gf_kfdb* db, int32_t counts[6], gf_keyframe_db* out, int32_t* inv_words, int32_t* inv_off,
+                 int32_t* inv_kf, const int32_t caps[6]);
 /* NULL detaches (Relocalisation then finds no candidate). The stream's
- * keyframes' query state (GF_FE_RELOC) is reset. */
+ * keyframes' query state (GF_FE_RELOC) is reset. With a growable database
+ * attached, the candidate scratch of the step is laid out for its max_kf, so a
+ * captured graph stays valid while the database grows. */
 int gf_frontend_set_kfdb(gf_frontend* fe, int stream, gf_kfdb* db);
 /* The vocabulary of Frame::ComputeBoW for relocalisation (mpORBVocabulary);
  * the caller keeps it alive while the front end steps. */
@@ -2095,13 +2130,33 @@ typedef struct gf_map_delta {
  * GF_ERR_CAP above 64 keyframes, map_cap points, 64 x keypoint-capacity slots
  * or observations, or nkf^2 covisibility entries (the capacities do not grow:
  * a map that outgrows them is the caller's to prune or window);
- * GF_ERR_UNSUPPORTED for an appended keyframe on a stream with a keyframe
- * database (gf_frontend_set_kfdb: the database and the graph must agree in
- * keyframes). A failing delta leaves every stream of the call untouched.
+ * GF_ERR_UNSUPPORTED for an appended keyframe on a stream whose keyframe
+ * database cannot follow it (gf_frontend_set_kfdb: the database and the graph
+ * must agree in keyframes): a fixed database, or a growable one without the
+ * keyframe's rows (gf_frontend_update_maps_kfdb). A failing delta leaves every
+ * stream of the call untouched.
  * After the call the map's cached copies are current: the float3 positions,
  * GF_FE_LAST_POS of the last frame's points, the graph's mp_bad. A stream not
  * named and every row not addressed are byte-identical before and after. */
 int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* deltas);
+/* The same call with the appended keyframes' database rows: kf_rows[i] is NULL
+ * or the rows of deltas[i]'s appended keyframes (nkf == n_new_kf, offsets from
+ * 0, keyframe k with as many keypoints as its new_kf_off row has slots), which
+ * join the stream's growable database (gf_kfdb_create_growable) in the same
+ * launches: KeyFrameDatabase::add. kf_rows NULL is gf_frontend_update_maps.
+ * On a stream with a database an appended keyframe needs a growable database
+ * and its rows (GF_ERR_UNSUPPORTED otherwise); rows on a stream without a
+ * database or with n_new_kf == 0, rows that differ from the slot counts and
+ * what gf_kfdb_append refuses: GF_ERR_ARG; above the database's max_kf or
+ * max_rows: GF_ERR_CAP. As for every failure of this call, no stream, graph
+ * or database of the call is touched. On success there is no host
+ * synchronisation and the call is legal after gf_frontend_capture: the step
+ * reads the stream's database record from device memory, and the last kernel
+ * flips it to the merged inverted file. Existing keyframes' GF_FE_RELOC rows
+ * are untouched; an appended keyframe's row is zero (a keyframe no query has
+ * touched). Staging for the rows is allocated by the first call of a size. */
+int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta* deltas,
+                                 const gf_keyframe_db* const* kf_rows);
 /* The keyframe graph the front end holds for a stream. counts[5] = nkf, nmp,
  * slots, covisibility entries, observations (always written); the arrays of
  * `out` are caller buffers with caps[3] = slot, covisibility and observation
