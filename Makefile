@@ -170,6 +170,14 @@ all: $(MAPUPDATEREF)
 $(MAPUPDATEREF): tests/helpers/mapupdate_ref.cpp include/gfslam/abi.h
 	$(CXX) $(ORCFLAGS) -shared $< -o $@
 
+# the tests' CPU restatement of gf_frontend_compact_maps: a request's verdict,
+# the pins and the restriction of one stream's flat arrays
+# (tests/test_mapcompact_cpu.py, tests/test_mapcompact_gpu.py), same flags
+MAPCOMPACTREF = tests/helpers/libmapcompactref.so
+all: $(MAPCOMPACTREF)
+$(MAPCOMPACTREF): tests/helpers/mapcompact_ref.cpp
+	$(CXX) $(ORCFLAGS) -shared $< -o $@
+
 # the tests' CPU restatement of the relocalisation database that grows:
 # KeyFrameDatabase::add into the packed inverted file, the append of database
 # rows and the verdicts (tests/test_kfdb_grow_cpu.py, tests/test_kfdb_grow_gpu.py),

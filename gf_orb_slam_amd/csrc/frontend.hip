@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mapcompact.h"
 #include "mapupdate.h"
 #include "newkeyframe.h"
 #include "reloc.h"
@@ -934,6 +935,9 @@ struct gf_frontend {
     uint8_t* kg_pin[2] = {nullptr, nullptr};
     size_t kg_bytes = 0, kg_pin_bytes[2] = {0, 0};
     std::vector<void*> kg_old_pins;
+    // map compaction (gf_frontend_compact_maps): the staged requests, the remap
+    // tables and the device's verdict per listed stream, allocated on first use
+    int32_t *mc_stage = nullptr, *mc_mp_remap = nullptr, *mc_kf_remap = nullptr, *mc_res = nullptr;
 };
 
 namespace {
@@ -1582,6 +1586,7 @@ static int fe_enable_covis(gf_frontend* fe) {
     A_(4 * B * fe->slot_cap, fe->cv_mp_obs);
 #undef A_
     GF_HIP(hipMemset(D.g2l, 0xff, 4 * B * M));
+    GF_HIP(hipMemset(fe->ref_kf, 0xff, 4 * B));  // no reference keyframe before the first step (a compaction pins it)
     D.map = wmap;
     D.nmp = fe->w_nmp;
     fe->wdesc = wdesc;
@@ -2235,6 +2240,9 @@ int mu_alloc(gf_frontend* fe) {
         GF_HIP(hipEventCreateWithFlags(&fe->mu_ev[i], hipEventDisableTiming));
     }
     FE_RC(fe_alloc(fe, fe->mu_bytes, &p));
+    // fe_alloc clears on the null stream, which the context's stream does not wait for: the first upload below
+    // must not be overtaken by the clear of its own buffer
+    GF_HIP(hipDeviceSynchronize());
     fe->mu_stage = (uint8_t*)p;  // last: marks the staging as complete
     return GF_OK;
 }
@@ -2413,6 +2421,207 @@ int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta
     A.obs_new = fe->mu_obs_new;
     FE_RC(gf::map_update_launch(fe->ctx, A, sh, s));
     return ngrow ? gf::kfdb_grow_launch(fe->ctx, fe->kg_stage, ngrow, gsh, s) : GF_OK;
+}
+
+// ---------------------------------------------------------------- map compaction
+// Staging and tables on first use, sized from the capacities; none afterwards.
+static int mc_alloc(gf_frontend* fe) {
+    if (fe->mc_stage) return GF_OK;
+    const size_t B = fe->D.B, M = fe->D.M, KC = gf_frontend::KF_CAP;
+    void* p = nullptr;
+    FE_RC(fe_alloc(fe, 4 * B * M, &p));
+    fe->mc_mp_remap = (int32_t*)p;
+    FE_RC(fe_alloc(fe, 4 * B * KC, &p));
+    fe->mc_kf_remap = (int32_t*)p;
+    FE_RC(fe_alloc(fe, 4 * B * gf::MC_RES_N, &p));
+    fe->mc_res = (int32_t*)p;
+    FE_RC(fe_alloc(fe, B * (sizeof(gf::McHdr) + 4 * (M + KC)), &p));
+    GF_HIP(hipDeviceSynchronize());  // the clears of fe_alloc run on the null stream: before the first upload
+    fe->mc_stage = (int32_t*)p;  // last: marks the allocation as complete
+    return GF_OK;
+}
+
+int gf_frontend_compact_maps(gf_frontend* fe, int nreq, const gf_map_compact* reqs, gf_map_remap* out) {
+    GF_CHECK(fe && nreq >= 0 && (nreq == 0 || (reqs && out)), GF_ERR_ARG, "bad arguments");
+    if (nreq == 0) return GF_OK;
+    GF_CHECK(fe->covis_set, GF_ERR_ARG, "map compaction needs keyframe graphs (gf_frontend_set_covis)");
+    GF_CHECK(!fe->extracted, GF_ERR_ARG, "the extracted frame has not been tracked (gf_frontend_step_track)");
+    FeDev& D = fe->D;
+    const int B = D.B, M = D.M, KC = gf_frontend::KF_CAP;
+    GF_CHECK(nreq <= B, GF_ERR_ARG, "a stream is named at most once");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    hipStream_t s = fe->ctx->stream;
+    // validate every request before anything is written
+    std::vector<uint8_t> named(B, 0);
+    bool any = false;
+    for (int i = 0; i < nreq; i++) {
+        const gf_map_compact& r = reqs[i];
+        const int b = r.stream;
+        GF_CHECK(b >= 0 && b < B, GF_ERR_ARG, "bad stream");
+        const std::string at = "stream " + std::to_string(b) + ": ";
+        GF_CHECK(!named[b], GF_ERR_ARG, at + "named twice");
+        named[b] = 1;
+        GF_CHECK(fe->has_covis[b], GF_ERR_ARG, at + "no keyframe graph (gf_frontend_set_covis)");
+        GF_CHECK(r.n_drop_kf >= 0 && r.n_drop_mp >= 0 && (!r.n_drop_kf || r.drop_kf) && (!r.n_drop_mp || r.drop_mp),
+                 GF_ERR_ARG, at + "negative count or null list");
+        GF_CHECK(out[i].kf_remap && out[i].mp_remap, GF_ERR_ARG, at + "null remap table");
+        if (fe->h_nmp[b] < 0) {  // the size was written behind the host's back (gf_dist_bcast_map)
+            GF_HIP(hipStreamSynchronize(s));
+            int32_t n = 0;
+            GF_HIP(hipMemcpy(&n, fe->g_nmp + b, 4, hipMemcpyDeviceToHost));
+            fe->h_nmp[b] = n;
+        }
+        const int nmp0 = fe->h_nmp[b], nkf0 = fe->h_kfc[b];
+        GF_CHECK(r.n_drop_kf <= nkf0 && r.n_drop_mp <= nmp0, GF_ERR_ARG, at + "more drops than items");
+        std::vector<uint8_t> mark((size_t)std::max(std::max(nmp0, nkf0), 1), 0);
+        for (int k = 0; k < r.n_drop_kf; k++) {
+            const int v = r.drop_kf[k];
+            GF_CHECK(v >= 0 && v < nkf0, GF_ERR_ARG, at + "dropped keyframe out of range");
+            GF_CHECK(!mark[v], GF_ERR_ARG, at + "keyframe " + std::to_string(v) + " listed twice");
+            mark[v] = 1;
+        }
+        std::fill(mark.begin(), mark.end(), 0);
+        for (int k = 0; k < r.n_drop_mp; k++) {
+            const int v = r.drop_mp[k];
+            GF_CHECK(v >= 0 && v < nmp0, GF_ERR_ARG, at + "dropped point out of range");
+            GF_CHECK(!mark[v], GF_ERR_ARG, at + "point " + std::to_string(v) + " listed twice");
+            mark[v] = 1;
+        }
+        const bool fixed_db = fe->rl_alloc && fe->h_kfdb[b].nkf && !fe->kfdb_obj[b];
+        GF_CHECK(!(r.n_drop_kf && fixed_db), GF_ERR_UNSUPPORTED,
+                 at + "a fixed keyframe database is attached: its keyframes cannot be dropped (use a database that "
+                      "grows, gf_kfdb_create_growable, or drop points only)");
+        any |= r.n_drop_kf > 0 || r.n_drop_mp > 0;
+    }
+    auto identity = [&](int i) {
+        const int b = reqs[i].stream;
+        out[i].nkf = fe->h_kfc[b];
+        out[i].nmp = fe->h_nmp[b];
+        out[i].n_kept_kf = out[i].n_kept_mp = 0;
+        for (int k = 0; k < out[i].nkf; k++) out[i].kf_remap[k] = k;
+        for (int k = 0; k < out[i].nmp; k++) out[i].mp_remap[k] = k;
+    };
+    if (!any) {  // nothing listed: nothing is launched
+        for (int i = 0; i < nreq; i++) identity(i);
+        return GF_OK;
+    }
+    FE_RC(mu_alloc(fe));  // the observation rebuild's tables
+    FE_RC(mc_alloc(fe));
+    // pack: headers, then the lists
+    const size_t hw = sizeof(gf::McHdr) / 4;
+    std::vector<int32_t> st(hw * (size_t)nreq);
+    std::vector<gf::McHdr> hdr(nreq);
+    for (int i = 0; i < nreq; i++) {
+        const gf_map_compact& r = reqs[i];
+        gf::McHdr& h = hdr[i];
+        h = gf::McHdr{};
+        h.stream = r.stream;
+        h.nmp0 = fe->h_nmp[r.stream];
+        h.nkf0 = fe->h_kfc[r.stream];
+        h.n_drop_kf = r.n_drop_kf;
+        h.n_drop_mp = r.n_drop_mp;
+        h.drop_kf = (int32_t)st.size();
+        st.insert(st.end(), r.drop_kf, r.drop_kf + r.n_drop_kf);
+        h.drop_mp = (int32_t)st.size();
+        st.insert(st.end(), r.drop_mp, r.drop_mp + r.n_drop_mp);
+    }
+    memcpy(st.data(), hdr.data(), sizeof(gf::McHdr) * (size_t)nreq);
+    GF_HIP(hipMemcpyAsync(fe->mc_stage, st.data(), 4 * st.size(), hipMemcpyHostToDevice, s));
+    gf::MapCompactArgs A{};
+    A.stage = fe->mc_stage;
+    A.L = nreq;
+    A.M = M;
+    A.cap = D.cap;
+    A.kf_cap = KC;
+    A.slot_cap = (long long)fe->slot_cap;
+    A.map = (gf_map_point*)fe->gm.map;
+    A.desc = (uint8_t*)fe->gm.desc;
+    A.pos = (float*)fe->gm.pos;
+    A.views = fe->gm.views;
+    A.H = fe->mp_H;
+    A.info = fe->mp_info;
+    A.info_lt = fe->mp_info_lt;
+    A.uv = fe->mp_uv;
+    A.upd = fe->gm.upd;
+    A.updated = fe->mp_updated;
+    A.mp_bad = fe->cv_mp_bad;
+    A.kf_bad = fe->cv_kf_bad;
+    static_assert(gf::RL_NC == gf_frontend::KF_CAP, "one GF_FE_RELOC row per graph keyframe");
+    A.reloc = fe->TL.rkf;
+    A.kf_mp_off = fe->cv_kf_mp_off;
+    A.kf_mp = fe->cv_kf_mp;
+    A.kf_cov_off = fe->cv_kf_cov_off;
+    A.kf_cov = fe->cv_kf_cov;
+    A.mp_obs_off = fe->cv_mp_obs_off;
+    A.mp_obs = fe->cv_mp_obs;
+    A.nmp = fe->g_nmp;
+    A.kfc = fe->d_kfc;
+    A.covis = fe->d_covis;
+    A.kp2mp = D.kp2mp;
+    A.nkp = D.nkp;
+    A.last_kp2mp = D.last_kp2mp;
+    A.last_nkp = D.last_nkp;
+    A.left = D.left;
+    A.nleft = D.stats + (size_t)GF_ST_NLEFT * B;
+    A.ref_kf = fe->ref_kf;
+    if (fe->kf_alloc) {
+        A.kf_state = fe->KA.state;
+        A.out_hdr = fe->KA.out_hdr;
+        A.out_slots = fe->KA.out_slots;
+    }
+    A.mp_remap = fe->mc_mp_remap;
+    A.kf_remap = fe->mc_kf_remap;
+    A.res = fe->mc_res;
+    A.obs_off_new = fe->mu_off_new;
+    A.obs_new = fe->mu_obs_new;
+    FE_RC(gf::map_compact_launch(fe->ctx, A, s));
+    // the device decided the pins: its verdict, the tables and what the host mirrors follow
+    GF_HIP(hipStreamSynchronize(s));
+    std::vector<int32_t> res((size_t)nreq * gf::MC_RES_N), kfr((size_t)nreq * KC), mpr((size_t)nreq * M);
+    GF_HIP(hipMemcpy(res.data(), fe->mc_res, 4 * res.size(), hipMemcpyDeviceToHost));
+    GF_HIP(hipMemcpy(kfr.data(), fe->mc_kf_remap, 4 * kfr.size(), hipMemcpyDeviceToHost));
+    GF_HIP(hipMemcpy(mpr.data(), fe->mc_mp_remap, 4 * mpr.size(), hipMemcpyDeviceToHost));
+    // everything down and checked first, so that a failure leaves no mirror half-updated
+    std::vector<std::vector<int32_t>> ko(nreq), oo(nreq);
+    for (int i = 0; i < nreq; i++) {
+        const int b = reqs[i].stream;
+        const int32_t* R = res.data() + (size_t)i * gf::MC_RES_N;
+        const int nkf1 = R[gf::MC_NKF], nmp1 = R[gf::MC_NMP];
+        GF_CHECK(nkf1 >= 0 && nkf1 <= hdr[i].nkf0 && nmp1 >= 0 && nmp1 <= hdr[i].nmp0, GF_ERR_HIP,
+                 "counts out of range on the device");
+        ko[i].assign(nkf1 + 1, 0);
+        oo[i].assign(nmp1 + 1, 0);
+        GF_HIP(hipMemcpy(ko[i].data(), fe->cv_kf_mp_off + (size_t)b * (KC + 1), 4 * ko[i].size(), hipMemcpyDeviceToHost));
+        GF_HIP(hipMemcpy(oo[i].data(), fe->cv_mp_obs_off + (size_t)b * (M + 1), 4 * oo[i].size(), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < nreq; i++) {
+        const int b = reqs[i].stream;
+        const int32_t* R = res.data() + (size_t)i * gf::MC_RES_N;
+        const int nkf1 = R[gf::MC_NKF], nmp1 = R[gf::MC_NMP];
+        out[i].nkf = nkf1;
+        out[i].nmp = nmp1;
+        out[i].n_kept_kf = R[gf::MC_KEPT_KF];
+        out[i].n_kept_mp = R[gf::MC_KEPT_MP];
+        memcpy(out[i].kf_remap, kfr.data() + (size_t)i * KC, 4 * (size_t)hdr[i].nkf0);
+        memcpy(out[i].mp_remap, mpr.data() + (size_t)i * M, 4 * (size_t)hdr[i].nmp0);
+        fe->h_nmp[b] = nmp1;
+        fe->h_kfc[b] = nkf1;
+        fe->h_nc[b] = R[gf::MC_NC];
+        fe->h_slots[b].resize(nkf1);
+        for (int k = 0; k < nkf1; k++) fe->h_slots[b][k] = ko[i][k + 1] - ko[i][k];
+        fe->h_obs_len[b].resize(nmp1);
+        for (int m = 0; m < nmp1; m++) fe->h_obs_len[b][m] = oo[i][m + 1] - oo[i][m];
+    }
+    // KeyFrameDatabase::erase: a stream's growable database follows its graph
+    for (int i = 0; i < nreq; i++) {
+        const int b = reqs[i].stream;
+        gf_kfdb* db = fe->rl_alloc ? fe->kfdb_obj[b] : nullptr;
+        if (!db || out[i].nkf == hdr[i].nkf0) continue;
+        FE_RC(gf::kfdb_erase(db, out[i].kf_remap, hdr[i].nkf0, fe->d_kfdb + b, s));
+        fe->h_kfdb[b] = gf::kfdb_dev(db);
+        GF_HIP(hipMemset(fe->TL.ncand + b, 0, 4));  // candidates named the old keyframe indices
+    }
+    return GF_OK;
 }
 
 int gf_frontend_get_covis(gf_frontend* fe, int stream, int32_t* counts, const gf_covis_out* out, const int32_t* caps) {

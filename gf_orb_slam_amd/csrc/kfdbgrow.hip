@@ -332,6 +332,234 @@ int kfdb_grow_launch(gf_ctx* ctx, const uint8_t* stage, int ndb, const KfdbGrowS
 
 }  // namespace gf
 
+// ------------------------------------------------------------------ erase
+// KeyFrameDatabase::erase (KeyFrameDatabase.cc:47-60) for the keyframes a map
+// compaction drops (gf_frontend_compact_maps): the kept keyframes' rows close
+// up in place, the inverted file is filtered and renumbered into the other
+// buffer set, the record is flipped last. The host knows which keyframes go
+// (the compaction has synchronised) and states old and new row offsets in the
+// header; the device moves. Rows move down, so a section is walked by one
+// workgroup in ascending chunks, all loads of a chunk before the barrier that
+// precedes its stores (as mapcompact.hip). The renumbering is monotone, so
+// every list keeps its order; a word whose list empties leaves the file.
+namespace {
+
+constexpr int KC_KF = gf::RL_NC;
+constexpr int KC_U = 4, KC_CHUNK = 256 * KC_U;
+enum { KC_KP = 0, KC_BOW, KC_NODE, KC_FEAT, KC_NFAM };
+enum { KC_SEC_KPS = 0, KC_SEC_DESC, KC_SEC_BW, KC_SEC_BV, KC_SEC_FN, KC_SEC_FS, KC_SEC_FF, KC_SEC_INV, KC_NSEC };
+
+struct KcHdr {
+    KfdbDev cur;       // the arrays as they are
+    KfdbDev next;      // the record after the call but for nw
+    KfdbDev* rec[2];   // the records to flip: the database's own, the front end's stream record or null
+    int32_t *scan, *pos;
+    int32_t nkf0, nkf1;
+    int32_t kr[KC_KF];                    // new keyframe index, -1 erased
+    int32_t old_off[KC_NFAM][KC_KF + 1];  // row offsets per keyframe: keypoints, BowVector entries, nodes, features
+    int32_t new_off[KC_NFAM][KC_KF + 1];  // by new keyframe index
+};
+
+// Items of W words, item j of keyframe k to new_off[kr[k]] + (j - old_off[k]); rebase: the moved values are
+// fv_start entries, offsets into fv_feats that follow their keyframe's features down.
+template <int W>
+__device__ void kc_move(uint32_t* base, const KcHdr* H, int fam, bool rebase) {
+    __shared__ int s_old[KC_KF + 1], s_new[KC_KF + 1], s_kr[KC_KF], s_sub[KC_KF];
+    const int t = threadIdx.x, nk = H->nkf0;
+    if (t <= KC_KF) {
+        s_old[t] = H->old_off[fam][min(t, nk)];
+        s_new[t] = H->new_off[fam][t];
+    }
+    if (t < KC_KF) {
+        const int kn = t < nk ? H->kr[t] : -1;
+        s_kr[t] = kn;
+        s_sub[t] = rebase && kn >= 0 ? H->old_off[KC_FEAT][t] - H->new_off[KC_FEAT][kn] : 0;
+    }
+    __syncthreads();
+    const long long total = (long long)s_old[nk] * W;
+    for (long long i0 = 0; i0 < total; i0 += KC_CHUNK) {
+        uint32_t v[KC_U];
+        long long d[KC_U];
+#pragma unroll
+        for (int u = 0; u < KC_U; u++) {
+            const long long i = min(i0 + t + 256 * u, total - 1);
+            const int item = (int)(i / W), c = (int)(i - (long long)item * W);
+            int lo = 0, hi = nk;  // the last k with s_old[k] <= item: its rows hold the item
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_old[mid] <= item) lo = mid; else hi = mid;
+            }
+            const int kn = s_kr[lo];
+            v[u] = base[i] - (uint32_t)s_sub[lo];
+            d[u] = i0 + t + 256 * u < total && kn >= 0 ? (long long)(s_new[kn] + item - s_old[lo]) * W + c : -1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KC_U; u++)
+            if (d[u] >= 0) base[d[u]] = v[u];
+    }
+}
+
+// mvInvertedFile without the erased keyframes, into the other buffer set; then the record(s).
+__device__ void kc_inverted(const KcHdr* H) {
+    __shared__ int s_wa[4], s_wb[4], s_kr[KC_KF];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nk = H->nkf0;
+    const int nw0 = H->rec[0]->nw;
+    const int32_t *W0 = H->cur.inv_words, *O0 = H->cur.inv_off, *K0 = H->cur.inv_kf;
+    int32_t *W1 = const_cast<int32_t*>(H->next.inv_words), *O1 = const_cast<int32_t*>(H->next.inv_off),
+            *K1 = const_cast<int32_t*>(H->next.inv_kf);
+    if (t < KC_KF) s_kr[t] = t < nk ? H->kr[t] : -1;
+    __syncthreads();
+    int ca = 0, cb = 0;  // words and list entries so far
+    for (int base = 0; base < nw0; base += 256) {
+        const int i = base + t;
+        int cnt = 0;
+        if (i < nw0)
+            for (int e = O0[i]; e < O0[i + 1]; e++) cnt += s_kr[min(max(K0[e], 0), KC_KF - 1)] >= 0;
+        const int fl = cnt > 0;
+        int a = fl, b = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int xa = __shfl_up(a, o, 64), xb = __shfl_up(b, o, 64);
+            if (lane >= o) {
+                a += xa;
+                b += xb;
+            }
+        }
+        if (lane == 63) {
+            s_wa[wave] = a;
+            s_wb[wave] = b;
+        }
+        __syncthreads();
+        int ba = 0, bb = 0, ta = 0, tb = 0;
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            if (w < wave) {
+                ba += s_wa[w];
+                bb += s_wb[w];
+            }
+            ta += s_wa[w];
+            tb += s_wb[w];
+        }
+        if (fl) {
+            const int j = ca + ba + a - 1;
+            int at = cb + bb + b - cnt;
+            W1[j] = W0[i];
+            O1[j] = at;
+            for (int e = O0[i]; e < O0[i + 1]; e++) {
+                const int kn = s_kr[min(max(K0[e], 0), KC_KF - 1)];
+                if (kn >= 0) K1[at++] = kn;
+            }
+        }
+        ca += ta;
+        cb += tb;
+        __syncthreads();
+    }
+    if (t == 0) O1[ca] = cb;
+    // the record word by word, as k_kg_finish
+    constexpr int RW = (int)(sizeof(KfdbDev) / 4), NW_AT = (int)(offsetof(KfdbDev, nw) / 4);
+    if (t < RW) {
+        int32_t* r0 = reinterpret_cast<int32_t*>(H->rec[0]);
+        int32_t* r1 = reinterpret_cast<int32_t*>(H->rec[1]);
+        int32_t w = reinterpret_cast<const int32_t*>(&H->next)[t];
+        if (t == NW_AT) w = ca;
+        r0[t] = w;
+        if (r1) r1[t] = w;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_kc_erase(const KcHdr* H) {
+    const KfdbDev& v = H->cur;
+    auto W = [](const void* p) { return reinterpret_cast<uint32_t*>(const_cast<void*>(p)); };
+    switch (blockIdx.x) {  // uniform
+    case KC_SEC_KPS: kc_move<(int)(sizeof(gf_keypoint) / 4)>(W(v.kps), H, KC_KP, false); break;
+    case KC_SEC_DESC: kc_move<8>(W(v.desc), H, KC_KP, false); break;
+    case KC_SEC_BW: kc_move<1>(W(v.bow_words), H, KC_BOW, false); break;
+    case KC_SEC_BV: kc_move<2>(W(v.bow_values), H, KC_BOW, false); break;
+    case KC_SEC_FN: kc_move<1>(W(v.fv_nodes), H, KC_NODE, false); break;
+    case KC_SEC_FS:
+        kc_move<1>(W(v.fv_start), H, KC_NODE, true);
+        if (threadIdx.x == 0) W(v.fv_start)[H->new_off[KC_NODE][H->nkf1]] = (uint32_t)H->new_off[KC_FEAT][H->nkf1];
+        break;
+    case KC_SEC_FF: kc_move<1>(W(v.fv_feats), H, KC_FEAT, false); break;
+    default: kc_inverted(H); break;
+    }
+}
+
+}  // namespace
+
+namespace gf {
+
+int kfdb_erase(gf_kfdb* d, const int32_t* kf_remap, int nkf0, KfdbDev* fe_rec, hipStream_t s) {
+    GF_CHECK(d && kf_remap && d->growable, GF_ERR_ARG, "erasing keyframes needs a database that grows");
+    GF_CHECK(nkf0 == d->dev.nkf && nkf0 <= KC_KF, GF_ERR_ARG, "the database and the keyframe graph differ in keyframes");
+    static_assert(sizeof(gf_keypoint) % 4 == 0, "keypoints move as words");
+    GF_HIP(hipSetDevice(d->device));
+    GF_HIP(hipStreamSynchronize(s));
+    const KfdbDev v = d->dev;
+    std::vector<int32_t> off[3], fs((size_t)d->nn + 1, 0);
+    const int32_t* src[3] = {v.kp_off, v.bow_off, v.fv_off};
+    for (int f = 0; f < 3; f++) {
+        off[f].assign(nkf0 + 1, 0);
+        if (nkf0) GF_HIP(hipMemcpy(off[f].data(), src[f], 4 * off[f].size(), hipMemcpyDeviceToHost));
+    }
+    if (nkf0) GF_HIP(hipMemcpy(fs.data(), v.fv_start, 4 * fs.size(), hipMemcpyDeviceToHost));
+    GF_CHECK(off[0][nkf0] == d->nk && off[1][nkf0] == d->nb && off[2][nkf0] == d->nn, GF_ERR_HIP,
+             "database offsets on the device differ from the host's counts");
+    KcHdr h{};
+    int nkf1 = 0;
+    for (int k = 0; k <= nkf0; k++) {
+        for (int f = 0; f < 3; f++) h.old_off[f][k] = off[f][k];
+        h.old_off[KC_FEAT][k] = fs[off[2][k]];
+    }
+    for (int k = 0; k < nkf0; k++) {
+        h.kr[k] = kf_remap[k];
+        if (kf_remap[k] < 0) continue;
+        GF_CHECK(kf_remap[k] == nkf1, GF_ERR_ARG, "the keyframe remap is not a stable renumbering");
+        for (int f = 0; f < KC_NFAM; f++)
+            h.new_off[f][nkf1 + 1] = h.new_off[f][nkf1] + (h.old_off[f][k + 1] - h.old_off[f][k]);
+        nkf1++;
+    }
+    for (int k = nkf0; k < KC_KF; k++) h.kr[k] = -1;
+    for (int f = 0; f < KC_NFAM; f++)
+        for (int k = nkf1 + 1; k <= KC_KF; k++) h.new_off[f][k] = h.new_off[f][nkf1];
+    const int side1 = d->side ^ 1;
+    h.cur = v;
+    h.next = v;
+    h.next.nkf = nkf1;
+    h.next.inv_words = d->inv_words[side1];
+    h.next.inv_off = d->inv_off[side1];
+    h.next.inv_kf = d->inv_kf[side1];
+    h.rec[0] = d->d_rec;
+    h.rec[1] = fe_rec;
+    h.scan = d->scan;
+    h.pos = d->pos;
+    h.nkf0 = nkf0;
+    h.nkf1 = nkf1;
+    int rc = grow_stage(d, sizeof(KcHdr));
+    if (rc) return rc;
+    GF_HIP(hipMemcpy(d->stage, &h, sizeof(h), hipMemcpyHostToDevice));
+    {
+        GF_PROF(d->ctx, s, "k_kc_erase");
+        GF_LAUNCH(k_kc_erase, KC_NSEC, 256, 0, s, reinterpret_cast<const KcHdr*>(d->stage));
+        GF_HIP(hipGetLastError());
+    }
+    GF_HIP(hipStreamSynchronize(s));
+    // the offsets the host computed, and its counts
+    int32_t* dst[3] = {(int32_t*)v.kp_off, (int32_t*)v.bow_off, (int32_t*)v.fv_off};
+    for (int f = 0; f < 3; f++)
+        GF_HIP(hipMemcpy(dst[f], h.new_off[f], 4 * ((size_t)nkf1 + 1), hipMemcpyHostToDevice));
+    d->dev = h.next;
+    d->side = side1;
+    d->nk = h.new_off[KC_KP][nkf1];
+    d->nb = h.new_off[KC_BOW][nkf1];
+    d->nn = h.new_off[KC_NODE][nkf1];
+    d->nf = h.new_off[KC_FEAT][nkf1];
+    return GF_OK;
+}
+
+}  // namespace gf
+
 extern "C" {
 
 int gf_kfdb_create_growable(gf_ctx* ctx, const gf_keyframe_db* db, int max_kf, int max_rows, gf_kfdb** out) {

@@ -154,6 +154,10 @@ size_t kfdb_grow_bytes(const KfdbGrowPlan& P);
 void kfdb_grow_pack(const KfdbGrowPlan& P, uint8_t* pin, int i, size_t& at, KfdbDev* fe_rec, gf_reloc_kf* rkf,
                     KfdbGrowShape& sh);
 int kfdb_grow_launch(gf_ctx* ctx, const uint8_t* stage, int ndb, const KfdbGrowShape& sh, hipStream_t s);
+// KeyFrameDatabase::erase for a map compaction: the keyframes whose kf_remap entry is -1 leave the growable
+// database (rows closed up in place, inverted file filtered into the other buffer set, records flipped).
+// Synchronises s before and after.
+int kfdb_erase(gf_kfdb* db, const int32_t* kf_remap, int nkf0, KfdbDev* fe_rec, hipStream_t s);
 
 // DetectRelocalisationCandidates for the streams that relocalise and their
 // SearchByBoW pairs (k_match_bow then runs over A.pairs).

@@ -143,6 +143,60 @@ class MapDelta:
             int(self.has_cov), self.kf_cov_off.ctypes.data, p(self.kf_cov))
 
 
+class MapCompactStruct(ctypes.Structure):
+    """gf_map_compact."""
+
+    _fields_ = [("stream", ctypes.c_int32), ("n_drop_kf", ctypes.c_int32), ("drop_kf", _P),
+                ("n_drop_mp", ctypes.c_int32), ("drop_mp", _P)]
+
+
+class MapRemapStruct(ctypes.Structure):
+    """gf_map_remap."""
+
+    _fields_ = [("nkf", ctypes.c_int32), ("nmp", ctypes.c_int32), ("kf_remap", _P), ("mp_remap", _P),
+                ("n_kept_kf", ctypes.c_int32), ("n_kept_mp", ctypes.c_int32)]
+
+
+class MapCompact:
+    """One stream's compaction request (abi.h gf_map_compact): the graph
+    keyframe indices and the map indices that leave the stream's map, each
+    list distinct. What frame state still holds stays (see MapRemap)."""
+
+    def __init__(self, stream: int, drop_kf=None, drop_mp=None):
+        self.stream = int(stream)
+        self.drop_kf = np.ascontiguousarray([] if drop_kf is None else drop_kf, np.int32).reshape(-1)
+        self.drop_mp = np.ascontiguousarray([] if drop_mp is None else drop_mp, np.int32).reshape(-1)
+
+    def empty(self) -> bool:
+        return not (len(self.drop_kf) or len(self.drop_mp))
+
+    def struct(self) -> MapCompactStruct:
+        p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        return MapCompactStruct(self.stream, len(self.drop_kf), p(self.drop_kf), len(self.drop_mp), p(self.drop_mp))
+
+
+class MapRemap:
+    """What a compaction did to one stream (abi.h gf_map_remap): the counts
+    after the call, ``kf_remap`` / ``mp_remap`` (old index -> new index, -1
+    dropped) over the old counts, and how many listed keyframes / points were
+    pinned by frame state and stayed."""
+
+    def __init__(self, stream: int, nkf: int, nmp: int, kf_remap, mp_remap, n_kept_kf: int = 0, n_kept_mp: int = 0):
+        self.stream, self.nkf, self.nmp = int(stream), int(nkf), int(nmp)
+        self.kf_remap = np.asarray(kf_remap, np.int32)
+        self.mp_remap = np.asarray(mp_remap, np.int32)
+        self.n_kept_kf, self.n_kept_mp = int(n_kept_kf), int(n_kept_mp)
+
+    def identity(self) -> bool:
+        return self.nkf == len(self.kf_remap) and self.nmp == len(self.mp_remap)
+
+    @staticmethod
+    def apply(remap, idx):
+        """Indices through a remap table; negative ones stay as they are."""
+        idx = np.asarray(idx)
+        return np.where(idx >= 0, np.asarray(remap, np.int32)[np.maximum(idx, 0)], idx).astype(np.int32)
+
+
 class DeviceCovisGraph:
     """The same arrays resident on the device (torch allocations as plumbing)."""
 

@@ -376,6 +376,37 @@ class FrontEnd:
             if d.kf_rows is not None and db is not None:
                 db.extend(d.kf_rows)
 
+    def compact_maps(self, requests) -> list:
+        """gf_frontend_compact_maps: drop keyframes and points from the stream
+        maps and keyframe graphs in place (a localmap.MapCompact or a list of
+        them, one per stream at most), renumbering every index the front end
+        holds. Items frame state still holds are pinned and stay. Behind the
+        last step, legal after capture_graph(); synchronises once. -> one
+        localmap.MapRemap per request. A refused request (GFError) leaves
+        every stream of the call untouched."""
+        from .localmap import MapCompact, MapCompactStruct, MapRemap, MapRemapStruct
+
+        rs = [requests] if isinstance(requests, MapCompact) else list(requests)
+        if not rs:
+            return []
+        arr = (MapCompactStruct * len(rs))(*[r.struct() for r in rs])
+        kf = [np.full(64, -1, np.int32) for _ in rs]
+        mp = [np.full(max(self.M, 1), -1, np.int32) for _ in rs]
+        out = (MapRemapStruct * len(rs))(*[MapRemapStruct(0, 0, k.ctypes.data, m.ctypes.data, 0, 0)
+                                           for k, m in zip(kf, mp)])
+        old = []  # the counts before the call: the lengths of the remap tables
+        for r in rs:
+            counts = np.zeros(5, np.int32)
+            rc = lib().gf_frontend_get_covis(self.handle, r.stream, ptr(counts), None, None)
+            old.append((int(counts[0]), int(counts[1])) if rc == 0 else (0, 0))  # refused below with its reason
+        check(lib().gf_frontend_compact_maps(self.handle, len(rs), arr, out))
+        for i, r in enumerate(rs):  # a growable database's host arrays follow the device (KeyFrameDatabase::erase)
+            db = getattr(self, "_kfdbs", {}).get(r.stream)
+            if db is not None and db.growable and out[i].nkf < old[i][0]:
+                db.erase(kf[i][:old[i][0]])
+        return [MapRemap(r.stream, o.nkf, o.nmp, kf[i][:old[i][0]].copy(), mp[i][:old[i][1]].copy(), o.n_kept_kf,
+                         o.n_kept_mp) for i, (r, o) in enumerate(zip(rs, out))]
+
     def covis(self, stream: int) -> dict:
         """gf_frontend_get_covis: the keyframe graph the front end holds for
         the stream, as the dict of arrays set_covis takes."""
@@ -728,6 +759,38 @@ class KeyframeDB:
                 self._buf = None
                 setattr(self, k, np.ascontiguousarray(np.concatenate([cur, new]), cur.dtype))
         self.nkf += rows.nkf
+
+    def erase(self, kf_remap) -> None:
+        """The host arrays without the keyframes whose ``kf_remap`` entry is -1
+        (what the device holds after ``FrontEnd.compact_maps`` dropped them):
+        the kept keyframes' rows closed up, offsets rebased."""
+        keep = np.nonzero(np.asarray(kf_remap)[:self.nkf] >= 0)[0]
+        fam = dict(kp_off=("kps", "desc"), bow_off=("bow_words", "bow_values"), fv_off=("fv_nodes",))
+        feat0 = self.fv_start[self.fv_off]  # the first feature of every keyframe
+        new = {}
+        for off, arrays in fam.items():
+            o = getattr(self, off)
+            rows = np.concatenate([np.arange(o[k], o[k + 1]) for k in keep]) if len(keep) else np.zeros(0, np.int64)
+            for a in arrays:
+                new[a] = getattr(self, a)[rows]
+            n = np.zeros(len(keep) + 1, np.int32)
+            n[1:] = np.cumsum((o[1:] - o[:-1])[keep])
+            new[off] = n
+            if off == "fv_off":  # fv_start: the nodes' offsets follow their keyframe's features down
+                nf = np.zeros(len(keep) + 1, np.int64)
+                nf[1:] = np.cumsum((feat0[1:] - feat0[:-1])[keep])
+                shift = np.repeat(feat0[keep] - nf[:-1], (o[1:] - o[:-1])[keep])
+                new["fv_start"] = np.concatenate([self.fv_start[rows] - shift, nf[-1:]]).astype(np.int32)
+                frows = (np.concatenate([np.arange(feat0[k], feat0[k + 1]) for k in keep]) if len(keep)
+                         else np.zeros(0, np.int64))
+                new["fv_feats"] = self.fv_feats[frows]
+        for k in self._ARRAYS:
+            a = np.ascontiguousarray(new[k], getattr(self, k).dtype)
+            if self._buf is not None:
+                self._buf[k][:len(a)] = a
+                a = self._buf[k][:len(a)]
+            setattr(self, k, a)
+        self.nkf = len(keep)
 
     def append(self, kps, desc=None, words=None, values=None, fv=None) -> None:
         """gf_kfdb_append: one more keyframe (index nkf) with its BowVector

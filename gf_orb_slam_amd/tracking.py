@@ -517,6 +517,60 @@ def _changed_rows(off_a, flat_a, off_b, flat_b, n: int) -> np.ndarray:
     return np.nonzero(diff)[0]
 
 
+def restrict_graph(g, kf_remap, mp_remap) -> dict:
+    """The ``gf_covis_map`` arrays restricted to the kept keyframes and points
+    (remap tables: new index, -1 dropped) and renumbered, as
+    ``FrontEnd.compact_maps`` leaves them on the device: slot rows of dropped
+    keyframes gone, a slot that named a dropped point -1, observation rows and
+    covisibility lists filtered in order."""
+    kf_remap, mp_remap = np.asarray(kf_remap, np.int32), np.asarray(mp_remap, np.int32)
+    keep_kf, keep_mp = kf_remap >= 0, mp_remap >= 0
+    nkf, n = len(keep_kf), len(keep_mp)
+
+    def off_of(lens):
+        off = np.zeros(len(lens) + 1, np.int32)
+        off[1:] = np.cumsum(lens)
+        return off
+
+    srow = np.repeat(np.arange(nkf), np.diff(g["kf_mp_off"]))
+    sm = keep_kf[srow]
+    sv = g["kf_mp"][sm]
+    kf_mp = np.where(sv >= 0, mp_remap[np.maximum(sv, 0)], -1).astype(np.int32) if n else sv.astype(np.int32)
+    crow = np.repeat(np.arange(nkf), np.diff(g["kf_cov_off"]))
+    cm = keep_kf[crow] & keep_kf[g["kf_cov"]] if nkf else np.zeros(0, bool)
+    orow = np.repeat(np.arange(n), np.diff(g["mp_obs_off"]))
+    om = keep_mp[orow] & keep_kf[g["mp_obs"]] if nkf else np.zeros(len(orow), bool)
+    return dict(kf_bad=np.asarray(g["kf_bad"])[keep_kf].astype(np.uint8),
+                kf_mp_off=off_of(np.diff(g["kf_mp_off"])[keep_kf]), kf_mp=kf_mp,
+                kf_cov_off=off_of(np.bincount(crow[cm], minlength=nkf)[keep_kf]),
+                kf_cov=kf_remap[g["kf_cov"][cm]].astype(np.int32),
+                mp_bad=np.asarray(g["mp_bad"])[keep_mp].astype(np.uint8),
+                mp_obs_off=off_of(np.bincount(orow[om], minlength=n)[keep_mp]),
+                mp_obs=kf_remap[g["mp_obs"][om]].astype(np.int32))
+
+
+def _graph_through(m, mp_id, kf_id) -> dict:
+    """:func:`covis_graph_from_loopmap` of the points ``mp_id`` and keyframes
+    ``kf_id`` of a ``LoopMap`` (ascending ids), in their positions: what a
+    front end that holds exactly those holds."""
+    mp_index, kf_index = np.full(len(m.mps), -1, np.int32), np.full(m.nkf, -1, np.int32)
+    mp_index[mp_id] = np.arange(len(mp_id), dtype=np.int32)
+    kf_index[kf_id] = np.arange(len(kf_id), dtype=np.int32)
+
+    def through(ids, index):
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        return np.where(ids >= 0, index[np.maximum(ids, 0)], -1).astype(np.int32) if len(index) else ids
+
+    kf_mp_off, kf_mp = _csr([through(m.slots[k], mp_index) for k in kf_id])
+    cov = [through(m.ordered[k], kf_index) for k in kf_id]
+    kf_cov_off, kf_cov = _csr([c[c >= 0] for c in cov])
+    obs = [through(sorted(m.obs[p]), kf_index) for p in mp_id]  # ascending ids stay ascending: the remap is monotone
+    mp_obs_off, mp_obs = _csr([o[o >= 0] for o in obs])
+    return dict(kf_bad=np.asarray(m.kf_bad)[kf_id].astype(np.uint8), kf_mp_off=kf_mp_off, kf_mp=kf_mp,
+                kf_cov_off=kf_cov_off, kf_cov=kf_cov, mp_bad=np.asarray(m.mp_bad)[mp_id].astype(np.uint8),
+                mp_obs_off=mp_obs_off, mp_obs=mp_obs)
+
+
 class MapFeedback:
     """Carries a ``LocalMapper``'s result back into the map a front-end stream
     tracks (``FrontEnd.update_maps``): a host shadow of what the front end
@@ -527,10 +581,15 @@ class MapFeedback:
     growable ``KeyframeDB``, the delta carries the new keyframes' database rows
     (``kf_kps`` / ``kf_desc`` / ``kf_bow`` / ``kf_fv`` of the LoopMap).
 
-    The id mapping is the identity: the LoopMap's point id is the map index,
-    its keyframe index the graph index, and both only grow. Anything else (a
-    map smaller than the shadow, an existing keyframe whose slot count changed,
-    a bad point or keyframe that is good again) raises ``ValueError``.
+    The id mapping starts as the identity: the LoopMap's point id is the map
+    index, its keyframe index the graph index, and both only grow. Anything
+    else (a map smaller than the shadow, an existing keyframe whose slot count
+    changed, a bad point or keyframe that is good again) raises ``ValueError``.
+    ``compact()`` drops keyframes and points from the front end's map
+    (``FrontEnd.compact_maps``) while the LoopMap never shrinks; from then on
+    ``mp_index`` / ``kf_index`` (LoopMap id -> front-end index, -1 = not held)
+    and their inverses ``mp_id`` / ``kf_id`` carry the mapping, and ``delta()``
+    goes through them.
 
     The shadow starts from the front end's own state (``fe.read`` /
     ``fe.covis``), or from ``shadow`` = dict(mp, desc, graph) when given."""
@@ -545,6 +604,10 @@ class MapFeedback:
         self.graph = {k: np.array(v, copy=True) for k, v in shadow["graph"].items()}
         if len(self.graph["mp_bad"]) != len(self.mp):
             raise ValueError("the shadow's graph and points differ in size")
+        self.mp_id = np.arange(len(self.mp), dtype=np.int32)  # front-end index -> LoopMap id
+        self.kf_id = np.arange(len(self.graph["kf_bad"]), dtype=np.int32)
+        self.mp_index, self.kf_index = self.mp_id.copy(), self.kf_id.copy()  # LoopMap id -> front-end index, -1 not held
+        self._identity = True
         self._next = None
         self.delta()  # raises where the map and the front end cannot share indices
         self._next = None
@@ -555,18 +618,21 @@ class MapFeedback:
         from .localmap import MapDelta
 
         m, g0 = self.map, self.graph
-        g1 = covis_graph_from_loopmap(m)
-        n0, n1, k0, k1 = len(self.mp), len(m.mps), len(g0["kf_bad"]), m.nkf
-        if n1 < n0 or k1 < k0:
+        if len(m.mps) < len(self.mp_index) or m.nkf < len(self.kf_index):
             raise ValueError("the map holds fewer points or keyframes than the front end: not the identity mapping")
+        # what the front end will hold: what it holds, then the LoopMap's new points and keyframes in id order
+        mp_id = np.concatenate([self.mp_id, np.arange(len(self.mp_index), len(m.mps), dtype=np.int32)])
+        kf_id = np.concatenate([self.kf_id, np.arange(len(self.kf_index), m.nkf, dtype=np.int32)])
+        g1 = covis_graph_from_loopmap(m) if self._identity else _graph_through(m, mp_id, kf_id)
+        n0, n1, k0, k1 = len(self.mp), len(mp_id), len(g0["kf_bad"]), len(kf_id)
         ns0 = int(g0["kf_mp_off"][k0])
         if not np.array_equal(g1["kf_mp_off"][:k0 + 1], g0["kf_mp_off"]):
             raise ValueError("an existing keyframe changed its slot count: not the identity mapping")
         if np.any(g0["mp_bad"].astype(bool) & ~g1["mp_bad"][:n0].astype(bool)) or \
                 np.any(g0["kf_bad"].astype(bool) & ~g1["kf_bad"][:k0].astype(bool)):
             raise ValueError("a bad point or keyframe is good again")
-        mp1 = np.ascontiguousarray(m.mps, MAP_POINT_DTYPE)
-        desc1 = np.ascontiguousarray(m.mp_desc, np.uint8).reshape(-1, 32)
+        mp1 = np.ascontiguousarray(np.asarray(m.mps)[mp_id], MAP_POINT_DTYPE)
+        desc1 = np.ascontiguousarray(np.asarray(m.mp_desc).reshape(-1, 32)[mp_id], np.uint8)
         rows = lambda a: a.view(np.uint8).reshape(len(a), -1)  # noqa: E731
         ch = np.nonzero(np.any(rows(mp1[:n0]) != rows(self.mp), axis=1) | np.any(desc1[:n0] != self.desc, axis=1))[0]
         bad_mp = np.nonzero(g1["mp_bad"][:n0].astype(bool) & ~g0["mp_bad"].astype(bool))[0]
@@ -584,25 +650,100 @@ class MapFeedback:
         db = getattr(self.fe, "_kfdbs", {}).get(self.stream)
         kf_rows = None
         if k1 > k0 and db is not None and db.growable:
-            for k in range(k0, k1):
+            for k in kf_id[k0:]:
                 if m.kf_bow[k] is None or m.kf_fv[k] is None:
                     raise ValueError(f"keyframe {k} has no BoW yet: it cannot join the keyframe database")
-            kf_rows = [(m.kf_kps[k], m.kf_desc[k], m.kf_bow[k][0], m.kf_bow[k][1], m.kf_fv[k]) for k in range(k0, k1)]
+            kf_rows = [(m.kf_kps[k], m.kf_desc[k], m.kf_bow[k][0], m.kf_bow[k][1], m.kf_fv[k]) for k in kf_id[k0:]]
         d = MapDelta(self.stream, new_mp=mp1[n0:], new_mp_desc=desc1[n0:], new_mp_bad=g1["mp_bad"][n0:],
                      set_mp_idx=ch, set_mp=mp1[ch], set_mp_desc=desc1[ch], bad_mp=bad_mp,
-                     new_kf=[np.asarray(s, np.int32) for s in m.slots[k0:]], new_kf_bad=g1["kf_bad"][k0:],
+                     new_kf=[g1["kf_mp"][g1["kf_mp_off"][k]:g1["kf_mp_off"][k + 1]] for k in range(k0, k1)],
+                     new_kf_bad=g1["kf_bad"][k0:],
                      bad_kf=bad_kf, slot_kf=skf, slot_idx=pos - g0["kf_mp_off"][skf], slot_val=g1["kf_mp"][pos],
                      obs_rows=obs_rows, kf_rows=kf_rows,
                      kf_cov=None if same_cov else [g1["kf_cov"][co[k]:co[k + 1]] for k in range(k1)])
-        self._next = dict(mp=mp1.copy(), desc=desc1.copy(), graph=g1)
+        self._next = dict(mp=mp1.copy(), desc=desc1.copy(), graph=g1, mp_id=mp_id, kf_id=kf_id, n_mp=len(m.mps),
+                          n_kf=m.nkf)
         return d
 
     def commit(self) -> None:
         """The shadow becomes the map of the last :meth:`delta`."""
         if self._next is None:
             raise RuntimeError("no delta to commit")
-        self.mp, self.desc, self.graph = self._next["mp"], self._next["desc"], self._next["graph"]
+        nx = self._next
+        self.mp, self.desc, self.graph = nx["mp"], nx["desc"], nx["graph"]
+        self._set_ids(nx["mp_id"], nx["kf_id"], nx["n_mp"], nx["n_kf"])
         self._next = None
+
+    def discard(self) -> None:
+        """Forget the last :meth:`delta` without committing it (it was not sent)."""
+        self._next = None
+
+    def _set_ids(self, mp_id, kf_id, n_mp: int, n_kf: int) -> None:
+        """The maps from the front end's indices to the LoopMap's ids (of n_mp
+        points and n_kf keyframes known so far) and their inverses."""
+        self.mp_id, self.kf_id = np.asarray(mp_id, np.int32), np.asarray(kf_id, np.int32)
+        self.mp_index, self.kf_index = np.full(n_mp, -1, np.int32), np.full(n_kf, -1, np.int32)
+        self.mp_index[self.mp_id] = np.arange(len(self.mp_id), dtype=np.int32)
+        self.kf_index[self.kf_id] = np.arange(len(self.kf_id), dtype=np.int32)
+
+    def default_drops(self, keep_kf=None):
+        """The default policy on what the front end holds (the shadow), in its
+        indices -> (drop_kf, drop_mp): every bad keyframe goes; if more than
+        ``keep_kf`` good keyframes remain, the newest keyframe stays, then its
+        ordered covisibility list in order, then the rest by recency, up to
+        ``keep_kf``; a bad point in no kept keyframe's slot goes, and so does a
+        good point that no kept keyframe observes. On a stream with a fixed
+        keyframe database attached every keyframe is kept (dropping one is
+        refused there), so the request is points-only; a growable database
+        follows the graph."""
+        g = self.graph
+        nkf, n = len(g["kf_bad"]), len(self.mp)
+        good = np.nonzero(~g["kf_bad"].astype(bool))[0]
+        kept = good
+        db = getattr(self.fe, "_kfdbs", {}).get(self.stream)
+        if db is not None and not getattr(db, "growable", False):
+            # a fixed keyframe database is attached: its keyframes cannot leave (GF_ERR_UNSUPPORTED), points can
+            kept = np.arange(nkf)
+        elif keep_kf is not None and len(good) > keep_kf:
+            newest = int(good[-1])
+            cov = g["kf_cov"][g["kf_cov_off"][newest]:g["kf_cov_off"][newest + 1]]
+            order = [newest] + [int(c) for c in cov if not g["kf_bad"][c]] + [int(k) for k in good[::-1]]
+            kept = np.sort(np.asarray(list(dict.fromkeys(order))[:max(int(keep_kf), 1)], np.int64))
+        keep_mask = np.zeros(nkf, bool)
+        keep_mask[kept] = True
+        srow = np.repeat(np.arange(nkf), np.diff(g["kf_mp_off"]))
+        in_slot = np.zeros(n, bool)
+        v = g["kf_mp"][keep_mask[srow]]
+        in_slot[v[v >= 0]] = True
+        orow = np.repeat(np.arange(n), np.diff(g["mp_obs_off"]))
+        seen = np.zeros(n, bool)
+        seen[orow[keep_mask[g["mp_obs"]]]] = True
+        bad = g["mp_bad"].astype(bool)
+        drop_mp = np.nonzero((bad & ~in_slot) | (~bad & ~seen))[0]
+        return np.nonzero(~keep_mask)[0].astype(np.int32), drop_mp.astype(np.int32)
+
+    def compact(self, drop_kf=None, drop_mp=None, keep_kf=None):
+        """Drop keyframes and points (front-end indices; both None: the default
+        policy of :meth:`default_drops`) from the front end's map with
+        ``FrontEnd.compact_maps``, and apply the returned remaps to the shadow
+        and the id maps. What frame state still holds is pinned and stays. The
+        LoopMap itself never shrinks. The shadow must be current (no delta
+        waiting for its commit). -> the ``localmap.MapRemap``."""
+        from .localmap import MapCompact
+
+        if self._next is not None:
+            raise RuntimeError("a delta waits for its commit")
+        if drop_kf is None and drop_mp is None:
+            drop_kf, drop_mp = self.default_drops(keep_kf)
+        rm = self.fe.compact_maps([MapCompact(self.stream, drop_kf, drop_mp)])[0]
+        if rm.identity():
+            return rm
+        keep_mp, keep_k = rm.mp_remap >= 0, rm.kf_remap >= 0
+        self.mp, self.desc = self.mp[keep_mp], self.desc[keep_mp]
+        self.graph = restrict_graph(self.graph, rm.kf_remap, rm.mp_remap)
+        self._set_ids(self.mp_id[keep_mp], self.kf_id[keep_k], len(self.mp_index), len(self.kf_index))
+        self._identity = False
+        return rm
 
 
 class KeyFrameInserter:
@@ -615,12 +756,14 @@ class KeyFrameInserter:
     without a mapper is left alone).
 
     point_ids[stream] (optional) maps the front end's map index to the
-    mapper's point id (identity by default; -1 stays -1).
+    mapper's point id (identity by default; -1 stays -1). A stream with a
+    ``MapFeedback`` translates through the feedback's ``mp_id`` instead, which
+    follows the compactions of the front end's map.
 
     feedback (optional): a ``MapFeedback`` per stream (a dict or a list) over
     the stream's mapper's map; ``feed_back()`` then carries the mappers' results
     back into the front end's maps. Off without it; a stream with ``point_ids``
-    cannot have one (the feedback needs the identity mapping)."""
+    cannot have one (the feedback keeps the id mapping itself)."""
 
     def __init__(self, fe, mappers, point_ids=None, feedback=None):
         self.fe = fe
@@ -651,7 +794,7 @@ class KeyFrameInserter:
             if b not in self.mappers:
                 continue
             slots = kf["slots"]
-            ids = self.point_ids.get(b)
+            ids = self.feedback[b].mp_id if b in self.feedback else self.point_ids.get(b)
             if ids is not None:
                 ids = np.asarray(ids, np.int32)
                 slots = np.where(slots >= 0, ids[np.maximum(slots, 0)], -1).astype(np.int32)
@@ -680,15 +823,41 @@ class KeyFrameInserter:
             self.fe.set_keyframe_state(stream, accept=1)
         return rep
 
-    def feed_back(self, streams=None) -> list:
+    def _passes(self, fb, d, lim) -> bool:
+        """The front end's counts after delta ``d`` pass a limit of ``lim``
+        (keyframes, points, slots, observations; the nkf^2 covisibility
+        capacity cannot be passed below the keyframe limit)."""
+        g = fb.graph
+        nkf = len(g["kf_bad"]) + len(d.new_kf_off) - 1
+        slots = len(g["kf_mp"]) + len(d.new_kf_mp)
+        old = np.diff(g["mp_obs_off"])
+        obs = len(g["mp_obs"]) + len(d.obs_kf) - int(old[d.obs_mp[d.obs_mp < len(old)]].sum())
+        return (nkf > lim["kf"] or len(fb.mp) + len(d.new_mp) > lim["mp"] or slots > lim["slots"] or obs > lim["slots"])
+
+    def feed_back(self, streams=None, compact_at=None) -> list:
         """The maps of the streams whose mapper ran since the last call (or of
         ``streams``) back into the front end: their ``MapFeedback.delta()``s in
         one ``FrontEnd.update_maps`` call, the shadows committed after it. In
         the reference this is no step at all: Tracking reads what LocalMapping
-        wrote through its pointers, under the map mutex. -> the deltas sent."""
+        wrote through its pointers, under the map mutex. -> the deltas sent.
+
+        compact_at (optional): dict(kf=, mp=, slots=, keep_kf=) of limits, each
+        defaulting to the front end's capacity (64 keyframes, map_cap points,
+        64 x keypoint-capacity slots and observations). A stream whose delta
+        would pass one is compacted first (``MapFeedback.compact`` with the
+        default policy and ``keep_kf``, by default half the keyframe limit),
+        and its delta is taken again through the new id maps."""
         which = sorted(self._ran if streams is None else streams)
         fbs = [self.feedback[b] for b in which if b in self.feedback]
         deltas = [fb.delta() for fb in fbs]
+        if compact_at is not None:
+            lim = dict(kf=64, mp=self.fe.M, slots=64 * self.fe.cap)
+            lim.update({k: v for k, v in compact_at.items() if k != "keep_kf"})
+            for i, fb in enumerate(fbs):
+                if self._passes(fb, deltas[i], lim):
+                    fb.discard()  # the delta is taken again after the compaction
+                    fb.compact(keep_kf=compact_at.get("keep_kf", max(lim["kf"] // 2, 1)))
+                    deltas[i] = fb.delta()
         live = [(fb, d) for fb, d in zip(fbs, deltas) if not d.empty()]
         if live:
             self.fe.update_maps([d for _, d in live])

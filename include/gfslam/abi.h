@@ -2063,7 +2063,8 @@ int gf_frontend_field(gf_frontend* fe, int field, size_t* bytes, void** d_ptr);
 /* ------------------------------------------------------------ map feedback
  * What LocalMapping wrote into the map since the tracker last looked, for one
  * stream, in the front end's own indices (map index, graph keyframe index;
- * both append-only, so every index the front end holds stays valid). In the
+ * this call only appends, so every index the front end holds stays valid;
+ * gf_frontend_compact_maps is what renumbers). In the
  * reference Tracking reads these through MapPoint* / KeyFrame* (Tracking.cc:
  * 3689-3852): here they are applied to the stream's map and keyframe graph in
  * place, on the context's stream behind the last step. Host arrays; an array
@@ -2129,7 +2130,7 @@ typedef struct gf_map_delta {
  * range, a row that is not ascending, a duplicate stream / point / slot;
  * GF_ERR_CAP above 64 keyframes, map_cap points, 64 x keypoint-capacity slots
  * or observations, or nkf^2 covisibility entries (the capacities do not grow:
- * a map that outgrows them is the caller's to prune or window);
+ * gf_frontend_compact_maps makes room in a map that reaches them);
  * GF_ERR_UNSUPPORTED for an appended keyframe on a stream whose keyframe
  * database cannot follow it (gf_frontend_set_kfdb: the database and the graph
  * must agree in keyframes): a fixed database, or a growable one without the
@@ -2174,6 +2175,66 @@ typedef struct gf_covis_out {
     int32_t* mp_obs;
 } gf_covis_out;
 int gf_frontend_get_covis(gf_frontend* fe, int stream, int32_t* counts, const gf_covis_out* out, const int32_t* caps);
+
+/* ---------------------------------------------------------- map compaction
+ * The inverse of the map feedback: keyframes and points leave a stream's map
+ * on the device, in place, and every index the front end holds is renumbered.
+ * It stands for Map::EraseMapPoint / Map::EraseKeyFrame (Map.cc) and, for the
+ * keyframe's database rows, KeyFrameDatabase::erase (KeyFrameDatabase.cc:
+ * 47-60). Used as a window (good keyframes and their points dropped so that a
+ * stream runs past the capacities) it stands for nothing: the reference's map
+ * is unbounded.
+ * The stream's map becomes the restriction of its map to the kept keyframes
+ * and points. Kept items keep their relative order (keyframe order is
+ * KeyFrame* order for UpdateReference). Every per-point row moves with its
+ * point, byte for byte: GF_FE_MAP, MAP_DESC, VIEWS, MP_H, MP_INFO, MP_UV,
+ * MP_UPD, the graph's mp_bad and the internal copies (float3 positions, packed
+ * ObsMat triangles). kf_bad and GF_FE_RELOC rows move with their keyframe.
+ * Slot rows of dropped keyframes disappear, kept rows close up, slot values
+ * are renumbered (a slot that named a dropped point becomes -1). Observation
+ * rows are filtered to the kept keyframes and renumbered (they stay
+ * ascending), covisibility lists are filtered in order and renumbered. Rows
+ * past the new counts keep whatever bytes they held.
+ * Pins: a point the next step can still read through frame state is kept even
+ * when listed: the points of GF_FE_KP2MP[0..nkp), GF_FE_LAST_KP2MP[0..last_nkp)
+ * and the slots of a pending outbox keyframe (GF_KF_PENDING); so is the
+ * keyframe the persistent reference-keyframe word names. The device decides
+ * (a mark pass before the scan) and reports: n_kept_* count the listed items
+ * that stayed, and the remap tables say where everything went. A pinned point
+ * whose keyframes are all gone keeps an empty observation row. Those holders
+ * are renumbered; GF_FE_LEFT[0..nleft) and GF_KF_REF, outputs of the last
+ * step, are renumbered with a dropped entry turned into -1.
+ * Everything is validated on the host first: GF_ERR_ARG for an index out of
+ * range, a duplicate, a stream named twice or a stream without a keyframe
+ * graph; GF_ERR_UNSUPPORTED for a non-empty drop_kf on a stream with a fixed
+ * (shareable) keyframe database attached (a points-only request is fine
+ * there). On a stream with a growable database (gf_kfdb_create_growable) a
+ * dropped keyframe's database rows go with it (keypoints, descriptors,
+ * BowVector, FeatureVector, offsets rebased), the inverted file is filtered
+ * and renumbered into the database's other buffer set and the record the step
+ * reads is flipped: KeyFrameDatabase::erase. A failing request leaves every stream of the call untouched;
+ * an empty request is a no-op with identity remaps. A stream not named is
+ * byte-identical before and after.
+ * The call runs behind the last step on the context's stream and is legal
+ * after gf_frontend_capture: no buffer moves, and the step reads every count
+ * from device memory. It synchronises once at the end (the result is
+ * device-decided) and brings the host mirrors up to date, so that
+ * gf_frontend_update_maps works against the compacted map with no read-back
+ * of its own. */
+typedef struct gf_map_compact {   /* one stream */
+    int32_t stream;
+    int32_t n_drop_kf;
+    const int32_t* drop_kf;       /* graph keyframe indices, distinct */
+    int32_t n_drop_mp;
+    const int32_t* drop_mp;       /* map indices, distinct            */
+} gf_map_compact;
+typedef struct gf_map_remap {     /* caller buffers, one per request  */
+    int32_t nkf, nmp;             /* after the call                   */
+    int32_t* kf_remap;            /* [old nkf] new index, -1 dropped (room for 64)       */
+    int32_t* mp_remap;            /* [old nmp] new index, -1 dropped (room for map_cap)  */
+    int32_t n_kept_kf, n_kept_mp; /* requested drops that were pinned */
+} gf_map_remap;
+int gf_frontend_compact_maps(gf_frontend* fe, int n, const gf_map_compact* reqs, gf_map_remap* out);
 
 /* ------------------------------------- NeedNewKeyFrame / CreateNewKeyFrame
  * `if(NeedNewKeyFrame()) CreateNewKeyFrame();` (Tracking.cc:896-897), the
