@@ -256,6 +256,9 @@ _PROTOS = {
     "gf_frontend_update_maps": [_P, _I, _P],
     "gf_frontend_update_maps_kfdb": [_P, _I, _P, _P],
     "gf_frontend_get_covis": [_P, _I, _P, _P, _P],
+    "gf_frontend_set_lifecycle": [_P, _I],
+    "gf_frontend_lifecycle_read": [_P, _P],
+    "gf_frontend_start_streams": [_P, _I, _P, _P],
     "gf_frontend_compact_maps": [_P, _I, _P, _P],
     "gf_need_new_keyframe": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "gf_need_new_keyframe_dev": [_P, _P, _P],

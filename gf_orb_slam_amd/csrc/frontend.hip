@@ -33,6 +33,7 @@
 #include "mapupdate.h"
 #include "newkeyframe.h"
 #include "reloc.h"
+#include "streamstart.h"
 #include "undist.h"
 
 namespace {
@@ -123,6 +124,7 @@ struct FeDev {
     int32_t* nmp_step;     // [B] without keyframe graphs: the map's size when TrackLocalMap runs, else 0
     float* th_m2;          // [B] SearchByProjection(F, local, th): 5 within 2 frames of a relocalisation (:3318-3320)
     int max_frames;        // mMaxFrames
+    int lifecycle;         // 1: a LOST verdict on at most 5 keyframes parks the stream (gf_frontend_set_lifecycle)
     // per-frame stage log (gf_frontend_set_time_log; tl_cap 0: off)
     int tl_cap;
     long long* tl_stamp;   // [tl_cap][GF_TL_NSITE] device clock at the stage boundaries
@@ -169,7 +171,9 @@ __global__ __launch_bounds__(256) void k_fe_begin(FeDev D) {
         const int since = min(T[GF_TR_SINCE] + 1, 1 << 30);
         T[GF_TR_SINCE] = since;
         const int kfc = D.kfc[b];
-        const int path = T[GF_TR_STATE] == 1 ? 3 : (T[GF_TR_VEL] && since >= 2 && !(kfc >= 0 && kfc < 4)) ? 0 : 2;
+        // a parked stream (NOT_INITIALIZED) takes no path: no search, no relocalisation
+        const int state = T[GF_TR_STATE];
+        const int path = state == 2 ? 4 : state == 1 ? 3 : (T[GF_TR_VEL] && since >= 2 && !(kfc >= 0 && kfc < 4)) ? 0 : 2;
         T[GF_TR_PATH] = path;
         T[GF_TR_OK] = 0;
         D.m3_nlast[b] = path == 0 ? D.last_nkp[b] : 0;
@@ -388,8 +392,15 @@ __global__ __launch_bounds__(256) void k_fe_post(FeDev D) {
         ok = !(T[GF_TR_SINCE] < D.max_frames && inl < 25) && inl >= 15;
         if (!ok) stat(D, GF_ST_FLAGS)[b] |= 16384;
     }
-    T[GF_TR_STATE] = ok ? 0 : 1;
-    T[GF_TR_VEL] = ok ? 1 : 0;  // mVelocity = cv::Mat() when lost
+    // a stream that entered parked leaves parked, its words as they were; with the
+    // lifecycle switch a LOST verdict on a map of at most 5 keyframes is
+    // Tracking::Reset (Tracking.cc:718-726): parked until the host starts it again
+    if (T[GF_TR_STATE] != 2) {
+        const int kfc = D.kfc[b];
+        const bool reset = !ok && D.lifecycle && kfc >= 0 && kfc <= 5;
+        T[GF_TR_STATE] = ok ? 0 : reset ? 2 : 1;
+        T[GF_TR_VEL] = ok ? 1 : 0;  // mVelocity = cv::Mat() when lost
+    }
     D.gate_post[b] = ok;
     D.nmp_post[b] = ok ? D.nmp[b] : 0;
     stat(D, GF_ST_NLEFT)[b] = n;
@@ -534,7 +545,8 @@ __global__ __launch_bounds__(256) void k_fe_end(FeDev D) {
         for (int u = 0; u < END_U; u++)
             if (i0 + 256 * u < 2 * n) dd[i0 + 256 * u] = v[u];
     }
-    const int m = D.gnmp[b];
+    // a parked stream's stamps stay: no frame of its map passes
+    const int m = D.track[(size_t)b * GF_TR_N + GF_TR_PATH] == 4 ? 0 : D.gnmp[b];
     int32_t* gu = D.gupd + (long long)b * D.M;
     for (int i0 = t; i0 < m; i0 += 256 * END_U) {
         int v[END_U];
@@ -935,6 +947,11 @@ struct gf_frontend {
     uint8_t* kg_pin[2] = {nullptr, nullptr};
     size_t kg_bytes = 0, kg_pin_bytes[2] = {0, 0};
     std::vector<void*> kg_old_pins;
+    // stream starts (gf_frontend_start_streams): the requests' headers and last-frame rows, device staging
+    // and two pinned buffers used in turn with mu_pin (the same event guards a turn's buffers)
+    uint8_t* ss_stage = nullptr;
+    uint8_t* ss_pin[2] = {nullptr, nullptr};
+    size_t ss_bytes = 0;
     // map compaction (gf_frontend_compact_maps): the staged requests, the remap
     // tables and the device's verdict per listed stream, allocated on first use
     int32_t *mc_stage = nullptr, *mc_mp_remap = nullptr, *mc_kf_remap = nullptr, *mc_res = nullptr;
@@ -979,6 +996,8 @@ void fe_free(gf_frontend* fe) {
         if (fe->mu_pin[i]) (void)hipHostFree(fe->mu_pin[i]);
         if (fe->kg_pin[i]) (void)hipHostFree(fe->kg_pin[i]);
         fe->kg_pin[i] = nullptr;
+        if (fe->ss_pin[i]) (void)hipHostFree(fe->ss_pin[i]);
+        fe->ss_pin[i] = nullptr;
         if (fe->mu_ev[i]) (void)hipEventDestroy(fe->mu_ev[i]);
         fe->mu_pin[i] = nullptr;
         fe->mu_ev[i] = nullptr;
@@ -2274,10 +2293,122 @@ int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* del
     return gf_frontend_update_maps_kfdb(fe, ndelta, deltas, nullptr);
 }
 
+namespace {
+
+// gf_frontend_start_streams reads a request's map as a delta against an empty
+// map: while its deltas are validated, the named streams' host mirrors and
+// their growable databases' host counts are empty. A call that is refused puts
+// them back (the destructor); one that goes ahead keeps the emptied ones,
+// which the shared code below then advances by the delta.
+struct StartMirrors {
+    struct Saved {
+        int b;
+        int32_t nmp, kfc, nc;
+        std::vector<int32_t> slots, obs_len;
+        gf_kfdb* db;
+        gf::KfdbHostCounts counts;
+    };
+    gf_frontend* fe;
+    std::vector<Saved> saved;
+    bool keep = false;
+    explicit StartMirrors(gf_frontend* f) : fe(f) {}
+    void empty(int b) {
+        Saved s;
+        s.b = b;
+        s.nmp = fe->h_nmp[b];
+        s.kfc = fe->h_kfc[b];
+        s.nc = fe->h_nc[b];
+        s.slots.swap(fe->h_slots[b]);
+        s.obs_len.swap(fe->h_obs_len[b]);
+        s.db = fe->rl_alloc ? fe->kfdb_obj[b] : nullptr;
+        if (s.db) {
+            s.counts = gf::kfdb_host_counts(s.db);
+            gf::kfdb_set_host_counts(s.db, gf::KfdbHostCounts{});
+        }
+        fe->h_nmp[b] = 0;
+        fe->h_kfc[b] = 0;
+        fe->h_nc[b] = 0;
+        saved.push_back(std::move(s));
+    }
+    ~StartMirrors() {
+        if (keep) return;
+        for (Saved& s : saved) {
+            fe->h_nmp[s.b] = s.nmp;
+            fe->h_kfc[s.b] = s.kfc;
+            fe->h_nc[s.b] = s.nc;
+            fe->h_slots[s.b].swap(s.slots);
+            fe->h_obs_len[s.b].swap(s.obs_len);
+            if (s.db) gf::kfdb_set_host_counts(s.db, s.counts);
+        }
+    }
+};
+
+inline size_t ss_stream_bytes(size_t cap) {
+    return sizeof(gf::SsHdr) + mu_a16(sizeof(gf_keypoint) * cap) + mu_a16(32 * cap) + mu_a16(4 * cap);
+}
+
+// What a start request asks beyond its map delta; nothing is written.
+int ss_validate(gf_frontend* fe, const gf_stream_start& r) {
+    const gf_map_delta& d = r.map;
+    const int b = d.stream;
+    const std::string at = "stream " + std::to_string(b) + ": ";
+    GF_CHECK(d.n_set_mp == 0 && d.n_bad_mp == 0 && d.n_bad_kf == 0 && d.n_slot == 0, GF_ERR_ARG,
+             at + "a start's map is read against an empty map: the set_*, bad_* and slot_* arrays must be empty");
+    GF_CHECK(r.n_last >= 0, GF_ERR_ARG, at + "negative keypoint count");
+    GF_CHECK(r.n_last <= fe->D.cap, GF_ERR_CAP, at + "the last frame holds more keypoints than the capacity");
+    GF_CHECK(r.n_last == 0 || (r.last_kps && r.last_desc && r.last_kp2mp), GF_ERR_ARG, at + "null last-frame array");
+    GF_CHECK(d.n_new_mp >= 0 && d.n_new_kf >= 0, GF_ERR_ARG, at + "negative count");
+    for (int i = 0; i < r.n_last; i++)
+        GF_CHECK(r.last_kp2mp[i] >= -1 && r.last_kp2mp[i] < d.n_new_mp, GF_ERR_ARG,
+                 at + "a last-frame keypoint names a point outside the new map");
+    GF_CHECK(d.n_new_kf > 0 ? (r.ref_kf >= 0 && r.ref_kf < d.n_new_kf) : r.ref_kf == -1, GF_ERR_ARG,
+             at + "the reference keyframe is not a keyframe of the new map");
+    GF_CHECK(r.frame_id >= 0 && r.since_reloc >= 0, GF_ERR_ARG, at + "negative frame id or frames since a relocalisation");
+    GF_CHECK(!(fe->rl_alloc && fe->h_kfdb[b].nkf && !fe->kfdb_obj[b]), GF_ERR_UNSUPPORTED,
+             at + "a fixed keyframe database is attached: a start needs a database that can be emptied "
+                  "(gf_kfdb_create_growable) or none");
+    return GF_OK;
+}
+
+// Staging of gf_frontend_start_streams on first use, sized from the capacities.
+int ss_alloc(gf_frontend* fe) {
+    if (fe->ss_stage) return GF_OK;
+    fe->ss_bytes = ss_stream_bytes((size_t)fe->D.cap) * (size_t)fe->D.B + 16;
+    for (int i = 0; i < 2; i++)  // a call that failed half-way left what it had allocated: it is used, not allocated again
+        if (!fe->ss_pin[i]) GF_HIP(hipHostMalloc((void**)&fe->ss_pin[i], fe->ss_bytes, hipHostMallocDefault));
+    void* p = nullptr;
+    FE_RC(fe_alloc(fe, fe->ss_bytes, &p));
+    GF_HIP(hipDeviceSynchronize());  // fe_alloc clears on the null stream: before the first upload
+    fe->ss_stage = (uint8_t*)p;      // last: marks the staging as complete
+    return GF_OK;
+}
+
+int fe_apply_deltas(gf_frontend* fe, int ndelta, const gf_map_delta* deltas, const gf_keyframe_db* const* kf_rows,
+                    const gf_stream_start* starts);
+
+}  // namespace
+
 int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta* deltas,
                                  const gf_keyframe_db* const* kf_rows) {
     GF_CHECK(fe && ndelta >= 0 && (ndelta == 0 || deltas), GF_ERR_ARG, "bad arguments");
     if (ndelta == 0) return GF_OK;
+    return fe_apply_deltas(fe, ndelta, deltas, kf_rows, nullptr);
+}
+
+int gf_frontend_start_streams(gf_frontend* fe, int n, const gf_stream_start* reqs, const gf_keyframe_db* const* kf_rows) {
+    GF_CHECK(fe && n >= 0 && (n == 0 || reqs), GF_ERR_ARG, "bad arguments");
+    if (n == 0) return GF_OK;
+    std::vector<gf_map_delta> deltas(n);
+    for (int i = 0; i < n; i++) deltas[i] = reqs[i].map;
+    return fe_apply_deltas(fe, n, deltas.data(), kf_rows, reqs);
+}
+
+namespace {
+
+// The deltas of gf_frontend_update_maps_kfdb; with `starts` (request i carries
+// delta i) the streams are cleared first and the deltas are their whole maps.
+int fe_apply_deltas(gf_frontend* fe, int ndelta, const gf_map_delta* deltas, const gf_keyframe_db* const* kf_rows,
+                    const gf_stream_start* starts) {
     GF_CHECK(fe->covis_set, GF_ERR_ARG, "map feedback needs keyframe graphs (gf_frontend_set_covis)");
     GF_CHECK(!fe->extracted, GF_ERR_ARG, "the extracted frame has not been tracked (gf_frontend_step_track)");
     const int B = fe->D.B, M = fe->D.M;
@@ -2298,6 +2429,12 @@ int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta
         }
     }
     // validate every delta before anything is written
+    StartMirrors mirrors(fe);
+    if (starts) {
+        for (int i = 0; i < ndelta; i++) FE_RC(ss_validate(fe, starts[i]));
+        FE_RC(ss_alloc(fe));
+        for (int i = 0; i < ndelta; i++) mirrors.empty(deltas[i].stream);
+    }
     std::vector<MuPlan> plans(ndelta);
     for (int i = 0; i < ndelta; i++) FE_RC(mu_validate(fe, deltas[i], kf_rows ? kf_rows[i] : nullptr, plans[i]));
     FE_RC(mu_alloc(fe));
@@ -2364,6 +2501,7 @@ int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta
         }
     }
     GF_CHECK(at <= fe->mu_bytes, GF_ERR_CAP, "the deltas exceed the staging sized from the capacities");
+    mirrors.keep = true;  // nothing below refuses: a started stream's mirrors begin at the empty map
     // the host mirrors follow the device tables
     for (int i = 0; i < ndelta; i++) {
         const gf_map_delta& d = deltas[i];
@@ -2386,11 +2524,80 @@ int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta
                            fe->TL.rkf + (size_t)b * gf::RL_NC, gsh);
         fe->h_kfdb[b] = gf::kfdb_dev(plans[i].grow.db);
     }
+    // the start requests: their headers, then every stream's last-frame rows
+    size_t sat = 0;
+    if (starts) {
+        uint8_t* sp = fe->ss_pin[turn];
+        sat = mu_a16(sizeof(gf::SsHdr) * (size_t)ndelta);
+        auto sput = [&](const void* src, size_t bytes) -> int64_t {
+            const size_t o = sat;
+            if (bytes) memcpy(sp + o, src, bytes);
+            sat += mu_a16(bytes);
+            return (int64_t)o;
+        };
+        for (int i = 0; i < ndelta; i++) {
+            const gf_stream_start& r = starts[i];
+            const int b = r.map.stream;
+            gf_kfdb* db = fe->rl_alloc ? fe->kfdb_obj[b] : nullptr;
+            gf::SsHdr h{};
+            h.stream = b;
+            h.n_last = r.n_last;
+            h.frame_id = r.frame_id;
+            h.since_reloc = std::min(r.since_reloc, 1 << 30);
+            h.ref_kf = r.ref_kf;
+            h.clear_db = db ? 1 : 0;
+            h.db_rec = db ? gf::kfdb_record(db) : nullptr;
+            h.kps = sput(r.last_kps, sizeof(gf_keypoint) * (size_t)r.n_last);
+            h.desc = sput(r.last_desc, 32 * (size_t)r.n_last);
+            h.kp2mp = sput(r.last_kp2mp, 4 * (size_t)r.n_last);
+            h.timestamp = r.timestamp;
+            memcpy(h.Tcw, r.Tcw, sizeof(h.Tcw));
+            memcpy(sp + sizeof(gf::SsHdr) * (size_t)i, &h, sizeof(h));
+            if (db && !plans[i].grow.db) fe->h_kfdb[b] = gf::kfdb_dev(db);  // emptied, no rows follow
+        }
+    }
     GF_HIP(hipMemcpyAsync(fe->mu_stage, pin, at, hipMemcpyHostToDevice, s));
     if (ngrow) GF_HIP(hipMemcpyAsync(fe->kg_stage, fe->kg_pin[turn], gat, hipMemcpyHostToDevice, s));
+    if (starts) GF_HIP(hipMemcpyAsync(fe->ss_stage, fe->ss_pin[turn], sat, hipMemcpyHostToDevice, s));
     GF_HIP(hipEventRecord(fe->mu_ev[turn], s));
     fe->mu_turn = turn ^ 1;
     FeDev& D = fe->D;
+    if (starts) {  // clear and install, in stream order before the map's rows and the database's
+        gf::StreamStartArgs S{};
+        S.stage = fe->ss_stage;
+        S.mu_stage = fe->mu_stage;
+        S.L = ndelta;
+        S.B = B;
+        S.M = M;
+        S.cap = D.cap;
+        S.kp2mp = D.kp2mp;
+        S.outl = D.outl;
+        S.last_kps = D.last_kps;
+        S.last_desc = D.last_desc;
+        S.last_nkp = D.last_nkp;
+        S.last_kp2mp = D.last_kp2mp;
+        S.last_outl = D.last_outl;
+        S.last_pos = D.last_pos;
+        S.Tcw_last = D.Tcw_last;
+        S.t_prev = D.t_prev;
+        S.t_cur = D.t_cur;
+        S.track = D.track;
+        S.kf_state = fe->kf_alloc ? fe->KA.state : nullptr;
+        S.ref_kf = fe->ref_kf;
+        S.nleft = D.nleft;
+        S.nlist = D.nlist;
+        S.st_nleft = D.stats + (size_t)GF_ST_NLEFT * B;
+        S.Xv = fe->Xv;
+        S.Xv_next = fe->Xv_next;
+        S.base = fe->base;
+        S.nmp = fe->g_nmp;
+        S.kfc = fe->d_kfc;
+        S.covis = fe->d_covis;
+        S.rkf = fe->TL.rkf;
+        S.ncand = fe->rl_alloc ? (int32_t*)fe->TL.ncand : nullptr;
+        S.fe_rec = fe->d_kfdb;
+        FE_RC(gf::stream_start_launch(fe->ctx, S, s));
+    }
     gf::MapUpdateArgs A{};
     A.stage = fe->mu_stage;
     A.L = ndelta;
@@ -2421,6 +2628,42 @@ int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta
     A.obs_new = fe->mu_obs_new;
     FE_RC(gf::map_update_launch(fe->ctx, A, sh, s));
     return ngrow ? gf::kfdb_grow_launch(fe->ctx, fe->kg_stage, ngrow, gsh, s) : GF_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------ park and reset
+int gf_frontend_set_lifecycle(gf_frontend* fe, int on) {
+    GF_CHECK(fe, GF_ERR_ARG, "null front end");
+    GF_CHECK(!fe->exec, GF_ERR_ARG, "set the lifecycle switch before capturing a graph");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    fe->D.lifecycle = on ? 1 : 0;
+    if (!on) return GF_OK;
+    // what the first gf_frontend_set_covis / gf_frontend_set_kfdb would allocate, so that a captured front end
+    // can take any stream's start later; a stream with no map and no graph begins parked on an empty graph
+    if (!fe->covis_set) FE_RC(fe_enable_covis(fe));
+    if (!fe->rl_alloc) FE_RC(fe_enable_reloc(fe));
+    // the staging of gf_frontend_start_streams and of the map update it goes through, so that a start on
+    // this front end never allocates or synchronises, the first one after a capture included
+    FE_RC(mu_alloc(fe));
+    FE_RC(ss_alloc(fe));
+    const gf_covis_map empty{};
+    const int32_t parked = 2;
+    for (int b = 0; b < fe->D.B; b++) {
+        if (fe->has_covis[b] || fe->h_nmp[b] != 0) continue;
+        FE_RC(gf_frontend_set_covis(fe, b, &empty));
+        GF_HIP(hipMemcpy(fe->D.track + (size_t)b * GF_TR_N + GF_TR_STATE, &parked, 4, hipMemcpyHostToDevice));
+    }
+    return GF_OK;
+}
+
+int gf_frontend_lifecycle_read(gf_frontend* fe, int32_t* state) {
+    GF_CHECK(fe && state, GF_ERR_ARG, "null arg");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    GF_HIP(hipMemcpy2D(state, 4, fe->D.track + GF_TR_STATE, 4 * GF_TR_N, 4, (size_t)fe->D.B, hipMemcpyDeviceToHost));
+    return GF_OK;
 }
 
 // ---------------------------------------------------------------- map compaction

@@ -206,6 +206,26 @@ int kfdb_bind(gf_kfdb* db, KfdbDev* rec) {
 
 void kfdb_unbind(gf_kfdb* db) { db->bound = false; }
 
+KfdbHostCounts kfdb_host_counts(const gf_kfdb* db) {
+    KfdbHostCounts c;
+    c.nkf = db->dev.nkf;
+    c.nk = db->nk;
+    c.nb = db->nb;
+    c.nn = db->nn;
+    c.nf = db->nf;
+    return c;
+}
+
+void kfdb_set_host_counts(gf_kfdb* db, const KfdbHostCounts& c) {
+    db->dev.nkf = c.nkf;
+    db->nk = c.nk;
+    db->nb = c.nb;
+    db->nn = c.nn;
+    db->nf = c.nf;
+}
+
+KfdbDev* kfdb_record(gf_kfdb* db) { return db->d_rec; }
+
 int kfdb_grow_validate(gf_kfdb* db, const gf_keyframe_db* rows, KfdbGrowPlan& P) {
     GF_CHECK(db && rows, GF_ERR_ARG, "null arg");
     GF_CHECK(db->growable, GF_ERR_ARG, "the keyframe database is fixed (gf_kfdb_create_growable makes one that grows)");

@@ -40,6 +40,8 @@ __global__ __launch_bounds__(256) void k_need_keyframe(gf_newkf_args A) {
     __shared__ int s_create;
     const int b = blockIdx.x, t = threadIdx.x;
     int32_t* S = A.state + (size_t)b * GF_KF_N;
+    // a parked stream (GF_TR_PATH 4) has no frame of its map: its words stay, SINCE included (uniform)
+    if (A.track[(size_t)b * GF_TR_N + GF_TR_PATH] == 4) return;
     const bool working = A.working[b] != 0;  // mState == WORKING (Tracking.cc:854)
     // phase 1: TrackedMapPoints of the reference keyframe: slots that are not
     // NULL (bad points count, as a non-NULL pointer does)

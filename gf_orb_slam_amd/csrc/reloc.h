@@ -154,6 +154,17 @@ size_t kfdb_grow_bytes(const KfdbGrowPlan& P);
 void kfdb_grow_pack(const KfdbGrowPlan& P, uint8_t* pin, int i, size_t& at, KfdbDev* fe_rec, gf_reloc_kf* rkf,
                     KfdbGrowShape& sh);
 int kfdb_grow_launch(gf_ctx* ctx, const uint8_t* stage, int ndb, const KfdbGrowShape& sh, hipStream_t s);
+// KeyFrameDatabase::clear for gf_frontend_start_streams: the host's counts of a
+// growable database, read, and set (to zero before the start's rows are
+// validated against the empty database; to what they were when the call is
+// refused). The device's record (kfdb_record) is emptied by the start's first
+// kernel, in stream order before the append that follows.
+struct KfdbHostCounts {
+    int nkf = 0, nk = 0, nb = 0, nn = 0, nf = 0;
+};
+KfdbHostCounts kfdb_host_counts(const gf_kfdb* db);
+void kfdb_set_host_counts(gf_kfdb* db, const KfdbHostCounts& c);
+KfdbDev* kfdb_record(gf_kfdb* db);
 // KeyFrameDatabase::erase for a map compaction: the keyframes whose kf_remap entry is -1 leave the growable
 // database (rows closed up in place, inverted file filtered into the other buffer set, records flipped).
 // Synchronises s before and after.

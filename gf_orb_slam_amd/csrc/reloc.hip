@@ -658,7 +658,8 @@ __global__ __launch_bounds__(TL_T) __attribute__((amdgpu_waves_per_eu(TL_WAVES_P
             todo &= todo - 1;
             int32_t* T = A.track + (size_t)b * GF_TR_N;
             const int path = T[GF_TR_PATH];
-            const bool ok = path == 3 ? relocalise(A, b, S) : track_previous_frame(A, b, S);
+            // path 4: a parked stream, no initial estimate at all
+            const bool ok = path == 4 ? false : path == 3 ? relocalise(A, b, S) : track_previous_frame(A, b, S);
             // nMatchesFound / num_to_match of the frame's matches (Tracking.cc:3195-3228)
             const int n = A.nkp[b];
             int c = 0;
@@ -669,7 +670,7 @@ __global__ __launch_bounds__(TL_T) __attribute__((amdgpu_waves_per_eu(TL_WAVES_P
                 stat_of(A, GF_ST_TO_MATCH)[b] = A.budget - c;
                 T[GF_TR_OK] = ok;
                 int fl = stat_of(A, GF_ST_FLAGS)[b];
-                fl |= path == 3 ? 4096 : 2048;
+                if (path != 4) fl |= path == 3 ? 4096 : 2048;
                 if (!ok) fl |= 8192;
                 if (path == 3 && ok) {
                     fl |= 32768;

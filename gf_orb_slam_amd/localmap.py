@@ -143,6 +143,52 @@ class MapDelta:
             int(self.has_cov), self.kf_cov_off.ctypes.data, p(self.kf_cov))
 
 
+class StreamStartStruct(ctypes.Structure):
+    """gf_stream_start."""
+
+    _fields_ = [("map", MapDeltaStruct), ("n_last", ctypes.c_int32), ("last_kps", _P), ("last_desc", _P),
+                ("last_kp2mp", _P), ("Tcw", ctypes.c_float * 16), ("timestamp", ctypes.c_double),
+                ("frame_id", ctypes.c_int32), ("since_reloc", ctypes.c_int32), ("ref_kf", ctypes.c_int32)]
+
+
+class StreamStart:
+    """One stream's beginning (abi.h gf_stream_start): ``map``, a MapDelta
+    read against an empty map (appended points and keyframes, observation
+    rows, covisibility lists, optionally ``kf_rows``; nothing rewritten, turned
+    bad or slot-written), the frame that becomes mLastFrame (undistorted
+    ``kps``, ``desc``, ``kp2mp`` into the new map with -1 for NULL, its pose
+    ``Tcw``, ``timestamp`` and ``frame_id`` = mnId, ``since_reloc`` = mnId -
+    mnLastRelocFrameId) and ``ref_kf``, mpReferenceKF as an index of the new
+    graph (None: the newest keyframe, -1 for a map without keyframes)."""
+
+    def __init__(self, map: MapDelta, kps=None, desc=None, kp2mp=None, Tcw=None, timestamp: float = 0.0,
+                 frame_id: int = 0, since_reloc: int | None = None, ref_kf: int | None = None):
+        from .orb import KEYPOINT_DTYPE
+
+        self.map = map
+        self.stream = map.stream
+        self.kps = np.ascontiguousarray(np.zeros(0, KEYPOINT_DTYPE) if kps is None else kps, KEYPOINT_DTYPE).reshape(-1)
+        self.desc = np.ascontiguousarray(np.zeros((0, 32), np.uint8) if desc is None else desc, np.uint8).reshape(-1, 32)
+        self.kp2mp = np.ascontiguousarray(np.full(len(self.kps), -1) if kp2mp is None else kp2mp, np.int32).reshape(-1)
+        if not len(self.kps) == len(self.desc) == len(self.kp2mp):
+            raise ValueError("stream start: the last frame's arrays differ in length")
+        self.Tcw = np.ascontiguousarray(np.eye(4) if Tcw is None else Tcw, np.float32).reshape(16)
+        self.timestamp, self.frame_id = float(timestamp), int(frame_id)
+        self.since_reloc = self.frame_id if since_reloc is None else int(since_reloc)  # mnLastRelocFrameId = 0
+        nkf = len(map.new_kf_off) - 1
+        self.ref_kf = nkf - 1 if ref_kf is None else int(ref_kf)
+
+    @property
+    def kf_rows(self):
+        return self.map.kf_rows
+
+    def struct(self) -> StreamStartStruct:
+        p = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        return StreamStartStruct(self.map.struct(), len(self.kps), p(self.kps), p(self.desc), p(self.kp2mp),
+                                 (ctypes.c_float * 16)(*self.Tcw.tolist()), self.timestamp, self.frame_id,
+                                 self.since_reloc, self.ref_kf)
+
+
 class MapCompactStruct(ctypes.Structure):
     """gf_map_compact."""
 

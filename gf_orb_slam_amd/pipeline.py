@@ -75,7 +75,9 @@ STATS = ["m3", "found", "to_match", "branch", "in_view", "local", "inl1", "inl2"
          "tpf", "ncand", "reloc", "ransac"]
 # GF_FE_TRACK columns and path codes
 TR = {"state": 0, "vel": 1, "since": 2, "path": 3, "query": 4, "ok": 5}
-PATHS = {0: "motion model", 1: "previous frame after the motion model", 2: "previous frame", 3: "relocalisation"}
+PATHS = {0: "motion model", 1: "previous frame after the motion model", 2: "previous frame", 3: "relocalisation",
+         4: "none (parked)"}
+STATES = {0: "WORKING", 1: "LOST", 2: "NOT_INITIALIZED"}  # GF_TR_STATE; 2: the stream is parked
 
 NSTAT = len(STATS)
 
@@ -406,6 +408,49 @@ class FrontEnd:
                 db.erase(kf[i][:old[i][0]])
         return [MapRemap(r.stream, o.nkf, o.nmp, kf[i][:old[i][0]].copy(), mp[i][:old[i][1]].copy(), o.n_kept_kf,
                          o.n_kept_mp) for i, (r, o) in enumerate(zip(rs, out))]
+
+    def enable_lifecycle(self, on: bool = True) -> None:
+        """gf_frontend_set_lifecycle: the reset rule of Tracking::GrabImage
+        (Tracking.cc:718-726) as part of every following step's verdict: a
+        stream that is LOST on a map of at most 5 keyframes is parked (state
+        2, NOT_INITIALIZED) until ``start_streams`` starts it again. Also
+        gives every stream without a map an empty keyframe graph in state 2,
+        so that a front end can begin empty. Before capture_graph()."""
+        check(lib().gf_frontend_set_lifecycle(self.handle, int(on)))
+
+    def lifecycle(self) -> np.ndarray:
+        """gf_frontend_lifecycle_read: GF_TR_STATE of every stream ([B] i32:
+        0 WORKING, 1 LOST, 2 NOT_INITIALIZED / parked); synchronises."""
+        st = np.zeros(self.B, np.int32)
+        check(lib().gf_frontend_lifecycle_read(self.handle, ptr(st)))
+        return st
+
+    def start_streams(self, requests) -> None:
+        """gf_frontend_start_streams: one stream's beginning on the device (a
+        localmap.StreamStart or a list of them, one per stream at most): the
+        stream then holds the request's map alone, its frame as mLastFrame,
+        fresh tracking and keyframe words and, with a growable KeyframeDB
+        attached, a database emptied and refilled with the request's
+        ``kf_rows`` (the host arrays follow). Behind the last step, without a
+        host synchronisation; legal after capture_graph(). A refused request
+        (GFError) leaves every stream of the call untouched."""
+        from .localmap import StreamStart, StreamStartStruct
+
+        rs = [requests] if isinstance(requests, StreamStart) else list(requests)
+        if not rs:
+            return
+        arr = (StreamStartStruct * len(rs))(*[r.struct() for r in rs])
+        rows = [r.kf_rows.struct() if r.kf_rows is not None else None for r in rs]
+        ptrs = None
+        if any(r is not None for r in rows):
+            ptrs = (ctypes.c_void_p * len(rs))(*[ctypes.addressof(r) if r is not None else None for r in rows])
+        check(lib().gf_frontend_start_streams(self.handle, len(rs), arr, ptrs))
+        for r in rs:  # the host arrays follow the device: KeyFrameDatabase::clear, then the rows
+            db = getattr(self, "_kfdbs", {}).get(r.stream)
+            if db is not None and db.growable:
+                db.clear()
+                if r.kf_rows is not None:
+                    db.extend(r.kf_rows)
 
     def covis(self, stream: int) -> dict:
         """gf_frontend_get_covis: the keyframe graph the front end holds for
@@ -759,6 +804,20 @@ class KeyframeDB:
                 self._buf = None
                 setattr(self, k, np.ascontiguousarray(np.concatenate([cur, new]), cur.dtype))
         self.nkf += rows.nkf
+
+    def clear(self) -> None:
+        """KeyFrameDatabase::clear on the host arrays (what the device holds
+        after ``FrontEnd.start_streams`` emptied the stream's database)."""
+        for k in self._ARRAYS:
+            n = 1 if k in ("kp_off", "bow_off", "fv_off", "fv_start") else 0  # the leading 0 of an offset row
+            a = getattr(self, k)
+            if self._buf is not None:
+                self._buf[k][:n] = 0
+                a = self._buf[k][:n]
+            else:
+                a = np.zeros((n,) + a.shape[1:], a.dtype)
+            setattr(self, k, a)
+        self.nkf = 0
 
     def erase(self, kf_remap) -> None:
         """The host arrays without the keyframes whose ``kf_remap`` entry is -1

@@ -612,6 +612,70 @@ class MapFeedback:
         self.delta()  # raises where the map and the front end cannot share indices
         self._next = None
 
+    @staticmethod
+    def empty_shadow() -> dict:
+        """The shadow of a stream that holds no map: no points, the empty graph."""
+        g = {k: np.zeros(1 if k.endswith("_off") else 0, np.uint8 if k.endswith("_bad") else np.int32)
+             for k in ("kf_bad", "kf_mp_off", "kf_mp", "kf_cov_off", "kf_cov", "mp_bad", "mp_obs_off", "mp_obs")}
+        return dict(mp=np.zeros(0, MAP_POINT_DTYPE), desc=np.zeros((0, 32), np.uint8), graph=g)
+
+    @classmethod
+    def starting(cls, fe, stream: int, loopmap) -> "MapFeedback":
+        """A feedback for a stream that is about to be started on ``loopmap``
+        (:meth:`start`): its shadow is the empty map, whatever the front end
+        holds for the stream now."""
+        return cls(fe, stream, loopmap, shadow=cls.empty_shadow())
+
+    def start(self, frame_kps, frame_desc, frame_id: int, timestamp: float, since_reloc=None):
+        """The ``localmap.StreamStart`` that begins this stream on its LoopMap
+        (as ``create_initial_map`` returns it; Tracking.cc:1302-1321), for
+        ``FrontEnd.start_streams``: the whole map as a delta against the empty
+        map (through ``covis_graph_from_loopmap``; with a growable KeyframeDB
+        on the stream, the keyframes' database rows from ``kf_bow`` /
+        ``kf_fv``), the given frame (the newest keyframe's: undistorted
+        keypoints and descriptors, its mnId and timestamp) as mLastFrame with
+        the newest keyframe's slot table as its map points and the newest
+        keyframe's pose, and the newest keyframe as mpReferenceKF. The id maps
+        and the shadow are then "the front end holds exactly this map": send
+        the request; if it is refused, make a new feedback.
+
+        A frame with more keypoints than the front end's capacity (the
+        initialiser's extractor asks for 2000, Tracking.cc:218) is reduced to
+        the keypoints that hold a map point, in order: SearchByProjection(Cur,
+        Last) (ORBmatcher.cc:2096-2098) and TrackPreviousFrame's WindowSearch
+        and SearchByProjection(F1, F2) (ORBmatcher.cc:995-998, 1101-1104) walk
+        mLastFrame.mvpMapPoints and skip NULL, so the dropped keypoints are
+        never read. If even those exceed the
+        capacity: GFError GF_ERR_CAP."""
+        from ._lib import GFError
+        from .localmap import StreamStart
+
+        m = self.map
+        if m.nkf < 1:
+            raise ValueError("the map holds no keyframe to start from")
+        shadow = self.empty_shadow()
+        self.mp, self.desc, self.graph = shadow["mp"], shadow["desc"], shadow["graph"]
+        self._set_ids(np.zeros(0, np.int32), np.zeros(0, np.int32), 0, 0)
+        self._identity = True
+        d = self.delta()
+        cur = m.nkf - 1
+        kps = np.ascontiguousarray(frame_kps, KEYPOINT_DTYPE).reshape(-1)
+        desc = np.ascontiguousarray(frame_desc, np.uint8).reshape(-1, 32)
+        kp2mp = np.asarray(m.slots[cur], np.int32).reshape(-1)
+        if not len(kps) == len(desc) == len(kp2mp):
+            self.discard()
+            raise ValueError("the frame and the newest keyframe differ in keypoints")
+        if len(kps) > self.fe.cap:
+            keep = np.nonzero(kp2mp >= 0)[0]
+            if len(keep) > self.fe.cap:
+                self.discard()
+                raise GFError(-3, f"the initial frame holds {len(keep)} matched keypoints, the front end {self.fe.cap}")
+            kps, desc, kp2mp = kps[keep], desc[keep], kp2mp[keep]
+        req = StreamStart(d, kps, desc, kp2mp, np.asarray(m.Tcw[cur], np.float32), timestamp, frame_id,
+                          since_reloc, ref_kf=cur)
+        self.commit()
+        return req
+
     def delta(self):
         """The ``MapDelta`` that takes the front end from the shadow to the
         LoopMap as it stands."""
@@ -633,7 +697,7 @@ class MapFeedback:
             raise ValueError("a bad point or keyframe is good again")
         mp1 = np.ascontiguousarray(np.asarray(m.mps)[mp_id], MAP_POINT_DTYPE)
         desc1 = np.ascontiguousarray(np.asarray(m.mp_desc).reshape(-1, 32)[mp_id], np.uint8)
-        rows = lambda a: a.view(np.uint8).reshape(len(a), -1)  # noqa: E731
+        rows = lambda a: a.view(np.uint8).reshape(len(a), a.dtype.itemsize)  # noqa: E731
         ch = np.nonzero(np.any(rows(mp1[:n0]) != rows(self.mp), axis=1) | np.any(desc1[:n0] != self.desc, axis=1))[0]
         bad_mp = np.nonzero(g1["mp_bad"][:n0].astype(bool) & ~g0["mp_bad"].astype(bool))[0]
         bad_kf = np.nonzero(g1["kf_bad"][:k0].astype(bool) & ~g0["kf_bad"].astype(bool))[0]
@@ -779,6 +843,64 @@ class KeyFrameInserter:
             if self.point_ids.get(b) is not None:
                 raise ValueError(f"stream {b}: map feedback needs the identity id mapping")
         self._ran = set()  # streams whose mapper ran since the last feed_back
+        self._parked = set()  # streams poll_resets has reported and start has not started again
+
+    def start(self, stream: int, loopmap, frame_kps, frame_desc, frame_id: int, timestamp: float, since_reloc=None,
+              mapper=None, voc=None):
+        """Begin ``stream`` on ``loopmap`` (a ``MonoInitializer``'s map, as
+        ``create_initial_map`` returns it) while the other streams keep
+        running: a ``MapFeedback`` whose shadow is this map, a ``LocalMapper``
+        over it (``mapper``, or one made with ``voc``), and the
+        ``FrontEnd.start_streams`` call with the initial frame as mLastFrame
+        (``MapFeedback.start``). A refused start (GFError) leaves the stream
+        and the inserter as they were. mbAcceptKeyFrames of the stream comes
+        back afterwards, as LocalMapping::ResetIfRequested leaves an idle
+        mapper. -> the ``localmap.StreamStart`` sent."""
+        from ._lib import GFError
+
+        stream = int(stream)
+        fb = MapFeedback.starting(self.fe, stream, loopmap)
+        req = fb.start(frame_kps, frame_desc, frame_id, timestamp, since_reloc)
+        self.fe.start_streams([req])
+        if mapper is None:
+            from .localmapping import LocalMapper
+
+            mapper = LocalMapper(loopmap, voc)
+        self.mappers[stream], self.feedback[stream] = mapper, fb
+        self.point_ids.pop(stream, None)
+        self.queue[stream] = []
+        self.stop_flags[stream] = ctypes.c_uint8(0)
+        self.stop_requested[stream] = False
+        self._ran.discard(stream)
+        self._parked.discard(stream)
+        try:
+            self.fe.set_keyframe_state(stream, accept=1, stop=0)
+        except GFError:  # the keyframe stage is off: no words to set
+            pass
+        return req
+
+    def poll_resets(self) -> list:
+        """``FrontEnd.lifecycle()``: every mapped stream that is newly parked
+        (state 2: it lost track on a map of at most 5 keyframes, the reset rule
+        of Tracking.cc:718-726) loses its mapper, its feedback and its queued
+        keyframes (LocalMapping::RequestReset / ResetIfRequested, LocalMapping.cc:625-655). -> their
+        indices, for the caller to run a ``MonoInitializer`` on them again and
+        :meth:`start` them."""
+        st = self.fe.lifecycle()
+        out = []
+        for b in sorted(set(self.mappers) | set(self.feedback)):
+            if int(st[b]) != 2 or b in self._parked:
+                continue
+            self.mappers.pop(b, None)
+            self.feedback.pop(b, None)
+            self.point_ids.pop(b, None)
+            self.queue.pop(b, None)
+            self.stop_flags.pop(b, None)
+            self.stop_requested.pop(b, None)
+            self._ran.discard(b)
+            self._parked.add(b)
+            out.append(b)
+        return out
 
     def pump(self) -> list:
         """Take the pending keyframes of the mapped streams' front end, insert

@@ -1840,12 +1840,14 @@ enum {
     GF_FE_NFIELDS
 };
 enum {
-    GF_TR_STATE = 0,    /* mState after the step: 0 WORKING, 1 LOST          */
+    GF_TR_STATE = 0,    /* mState after the step: 0 WORKING, 1 LOST, 2 NOT_INITIALIZED
+                           (parked: the step extracts the stream's frame and
+                           tracks nothing; see gf_frontend_set_lifecycle)    */
     GF_TR_VEL,          /* 1: mVelocity holds a motion, 0: empty              */
     GF_TR_SINCE,        /* mnId - mnLastRelocFrameId (saturates at 1 << 30)  */
     GF_TR_PATH,         /* initial estimate of the last step: 0 TrackWithMotionModel,
                            1 TrackPreviousFrame after it failed, 2 TrackPreviousFrame,
-                           3 Relocalisation                                  */
+                           3 Relocalisation, 4 none (the stream is parked)   */
     GF_TR_QUERY,        /* mnId of the last frame (the keyframe database's query id) */
     GF_TR_OK,           /* bOK of the last step's initial estimate           */
     GF_TR_N = 8
@@ -2158,6 +2160,107 @@ int gf_frontend_update_maps(gf_frontend* fe, int ndelta, const gf_map_delta* del
  * touched). Staging for the rows is allocated by the first call of a size. */
 int gf_frontend_update_maps_kfdb(gf_frontend* fe, int ndelta, const gf_map_delta* deltas,
                                  const gf_keyframe_db* const* kf_rows);
+/* ------------------------------------------- stream start, park and reset
+ * A stream whose GF_TR_STATE is 2 (NOT_INITIALIZED) is parked: the step
+ * extracts its frame as for every stream, but the frame is not tracked, not
+ * relocalised and creates no keyframe. Its carried state (map, graph, database
+ * record, GF_FE_RELOC row, last frame, velocity, GF_FE_RNG, per-point state,
+ * Xv / Xv_next / base, the GF_KF_* words) stays byte-identical however many
+ * steps pass; only the per-step outputs change: the current frame's keypoints,
+ * descriptors, count and match arrays, GF_FE_TCW (zeros, a fresh Frame's empty
+ * mTcw), GF_FE_T_CUR, the stats, GF_TR_QUERY, GF_TR_SINCE, GF_TR_PATH = 4 and
+ * GF_TR_OK = 0. The extraction of a parked stream still runs.
+ *
+ * gf_frontend_set_lifecycle(fe, on), before gf_frontend_capture like the other
+ * set calls; off is the default. When on, the step applies the reset rule of
+ * Tracking::GrabImage (Tracking.cc:718-726): a stream whose verdict is LOST and
+ * whose map holds at most 5 keyframes (the count the step reads for the < 4
+ * test of :602; a stream without a keyframe graph, count -1, never resets) goes
+ * to state 2 instead of 1. Nothing else is written: the map stays where it is
+ * (parking stands for mpKeyFrameDB->clear() / mpMap->clear() until the host
+ * reacts), so the host mirrors stay true, and the next gf_frontend_start_streams
+ * overwrites everything. Switching it on also allocates what the first
+ * gf_frontend_set_covis and gf_frontend_set_kfdb would allocate and gives every
+ * stream that has no map and no graph an empty graph (0 keyframes, 0 points) in
+ * state 2, so that a front end can begin empty and be captured. An empty
+ * growable database attaches to such a graph with gf_frontend_set_kfdb. It
+ * also allocates the staging of gf_frontend_start_streams and of the map
+ * update, so that no start on this front end allocates or synchronises;
+ * without it the first start (as the first gf_frontend_update_maps) allocates
+ * its staging and synchronises once.
+ * Which streams it parks is decided at the call: those with neither a map nor
+ * a graph at that moment. A parked stream leaves state 2 only through
+ * gf_frontend_start_streams or a write of GF_TR_STATE (GF_FE_TRACK):
+ * gf_frontend_set_map / gf_frontend_set_covis on a parked stream leave it
+ * parked. gf_frontend_bootstrap is the start of every stream at once and
+ * overrides parking: it sets every stream WORKING, a parked one included.
+ * gf_frontend_lifecycle_read: GF_TR_STATE of every stream ([B] i32), after a
+ * synchronisation. */
+int gf_frontend_set_lifecycle(gf_frontend* fe, int on);
+int gf_frontend_lifecycle_read(gf_frontend* fe, int32_t* state);
+/* One stream's beginning (Tracking::CreateInitialMap, Tracking.cc:1302-1321):
+ *   map: the whole new map as a delta read against an empty map (appended
+ *     points, appended keyframes with their slot rows, observation rows, the
+ *     covisibility lists; n_set_mp, n_bad_mp, n_bad_kf and n_slot must be 0);
+ *     map.stream names the stream.
+ *   the frame that becomes mLastFrame (:1308): n_last <= the keypoint capacity
+ *     undistorted keypoints, descriptors and kp2mp (indices of the new map, -1
+ *     NULL; no outliers), its pose, timestamp and mnId, and since_reloc =
+ *     mnId - mnLastRelocFrameId.
+ *   ref_kf: mpReferenceKF = pKFcur (:1315) as an index of the new graph (-1
+ *     only for a map without keyframes). */
+typedef struct gf_stream_start {
+    gf_map_delta map;
+    int32_t n_last;
+    const gf_keypoint* last_kps;
+    const uint8_t* last_desc;   /* [n_last][32] */
+    const int32_t* last_kp2mp;
+    float Tcw[16];
+    double timestamp;
+    int32_t frame_id, since_reloc;
+    int32_t ref_kf;
+} gf_stream_start;
+/* Start n streams (each named at most once; every one needs a keyframe graph,
+ * possibly the empty one of gf_frontend_set_lifecycle) in one upload and one
+ * set of launches on the context's stream behind the last step, with no host
+ * synchronisation on success (the staging is allocated by
+ * gf_frontend_set_lifecycle, else by the first call, which then synchronises
+ * once); legal after gf_frontend_capture. kf_rows is NULL
+ * or per request NULL / the database rows of the map's keyframes, as in
+ * gf_frontend_update_maps_kfdb. On success a named stream holds
+ *   the map alone: counts, points, descriptors, cached positions, mp_bad, slot
+ *     rows, observation rows and covisibility are those of the delta, the
+ *     per-point state of rows [0, nmp) that of fresh points (GF_FE_MP_UPD
+ *     -1000, GF_FE_VIEWS 0; MP_H / MP_INFO / MP_UV as gf_frontend_set_map
+ *     leaves them); rows past the new counts keep their bytes;
+ *   the last frame: GF_FE_LAST_* from the request (LAST_OUTLIER 0), LAST_POS
+ *     gathered from the new map on the device, TCW_LAST and T_PREV from the
+ *     request, T_CUR = T_PREV; KP2MP (-1) and OUTLIER (0) of the current frame
+ *     cleared; GF_FE_LEFT empty (GF_ST_NLEFT 0);
+ *   the tracking words: STATE 0, VEL 0 (mVelocity is empty after the
+ *     initialiser, so the next step takes TrackPreviousFrame), SINCE =
+ *     since_reloc, QUERY = frame_id, PATH 2, OK 1;
+ *   the keyframe words (when the stage is allocated): SINCE 0 (:1309), PENDING
+ *     0 (an untaken keyframe of the old map is dropped, as RequestReset empties
+ *     mlNewKeyFrames), ABORT 0, DECISION 0, REF and the persistent
+ *     reference-keyframe word = ref_kf; the other words stay;
+ *   Xv, Xv_next and base as gf_frontend_create leaves them (zeros); GF_FE_RNG
+ *     and GF_FE_VELOCITY untouched;
+ *   the database: a growable one is emptied (KeyFrameDatabase::clear) and then
+ *     holds exactly the given rows, inverted file rebuilt on the device; the
+ *     stream's GF_FE_RELOC rows are zero and no relocalisation candidate
+ *     survives. A fixed database: GF_ERR_UNSUPPORTED. Rows without a database:
+ *     GF_ERR_ARG.
+ * Validation on the host first, as gf_frontend_update_maps_kfdb against an
+ * empty map (ranges, ascending rows, duplicates, GF_ERR_CAP above 64
+ * keyframes, map_cap points, the slot / observation / covisibility capacities,
+ * the database's max_kf and max_rows), plus GF_ERR_ARG for a non-empty set_*,
+ * bad_* or slot_* array, kp2mp or ref_kf out of range, and GF_ERR_CAP for
+ * n_last above the keypoint capacity. A failing request leaves every stream,
+ * graph and database of the call untouched; a stream not named is
+ * byte-identical before and after; n == 0 launches nothing. */
+int gf_frontend_start_streams(gf_frontend* fe, int n, const gf_stream_start* reqs,
+                              const gf_keyframe_db* const* kf_rows);
 /* The keyframe graph the front end holds for a stream. counts[5] = nkf, nmp,
  * slots, covisibility entries, observations (always written); the arrays of
  * `out` are caller buffers with caps[3] = slot, covisibility and observation

@@ -402,6 +402,40 @@ inline bool NeedNewKeyFrame(const KeyFrameDecisionInput& in, bool* pbInterruptBA
     return need != 0;
 }
 
+/* ---------------------------------------------------------------- Tracking::Reset */
+/* Tracking::eTrackingState (Tracking.h:163-170) of a front-end stream from its
+ * GF_TR_STATE word: 0 WORKING, 1 LOST, 2 NOT_INITIALIZED (the stream is parked:
+ * the step extracts its frame and tracks nothing until gf_frontend_start_streams
+ * starts it again). */
+enum eTrackingState { SYSTEM_NOT_READY = -1, NO_IMAGES_YET = 0, NOT_INITIALIZED = 1, INITIALIZING = 2, WORKING = 3, LOST = 4 };
+inline eTrackingState TrackingState(int gfTrState) {
+    return gfTrState == 0 ? WORKING : gfTrState == 1 ? LOST : NOT_INITIALIZED;
+}
+/* The rule of Tracking::GrabImage (Tracking.cc:718-726) that calls
+ * Tracking::Reset (:4057-4098): the camera got lost soon after the
+ * initialisation. gf_frontend_set_lifecycle makes it part of the step's
+ * verdict; this is the same test on values, for a caller that tracks a single
+ * sequence through the host families. */
+inline bool ResetAfterLoss(eTrackingState state, int nKeyFramesInMap) {
+    return state == LOST && nKeyFramesInMap >= 0 && nKeyFramesInMap <= 5;
+}
+/* Tracking::Reset for a batched front end: switch the rule on (before
+ * gf_frontend_capture), and read which streams it has parked. A parked stream
+ * keeps its map on the device until gf_frontend_start_streams overwrites it,
+ * which stands for mpKeyFrameDB->clear() and mpMap->clear(); the host drops its
+ * mapper's queue for the stream (LocalMapping::RequestReset) when it sees
+ * NOT_INITIALIZED here. */
+inline void EnableReset(gf_frontend* pFrontEnd, bool bOn = true) {
+    if (gf_frontend_set_lifecycle(pFrontEnd, bOn ? 1 : 0) != GF_OK) throw std::runtime_error(gf_last_error());
+}
+inline std::vector<eTrackingState> TrackingStates(gf_frontend* pFrontEnd, int nStreams) {
+    std::vector<int32_t> st((size_t)nStreams);
+    if (gf_frontend_lifecycle_read(pFrontEnd, st.data()) != GF_OK) throw std::runtime_error(gf_last_error());
+    std::vector<eTrackingState> out;
+    for (int32_t s : st) out.push_back(TrackingState(s));
+    return out;
+}
+
 }  // namespace ORB_SLAM
 
 #endif /* GFSLAM_ORBSLAM_H */
