@@ -260,6 +260,8 @@ _PROTOS = {
     "gf_frontend_lifecycle_read": [_P, _P],
     "gf_frontend_start_streams": [_P, _I, _P, _P],
     "gf_frontend_compact_maps": [_P, _I, _P, _P],
+    "gf_frontend_force_relocalisation": [_P, _I, _P, _P],
+    "gf_frontend_reloc_candidates_read": [_P, _P, _P],
     "gf_need_new_keyframe": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "gf_need_new_keyframe_dev": [_P, _P, _P],
     "gf_frontend_set_keyframes": [_P, _I, _I, _I],

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void k_fe_begin(FeDev D) {
             D.ptrs[b] = D.bases[b] + (long long)idx * D.frame_stride;
         }
         D.t_cur[b] = D.t_cur[b] + D.dt;  // mCurrentFrame.mTimeStamp (mLastFrame's may be older after a loss)
-        // the initial estimate's path (Tracking.cc:602-628): LOST -> Relocalisation;
+        // the initial estimate's path (Tracking.cc:602-628): LOST or forced -> Relocalisation;
         // a velocity and >= 2 frames since a relocalisation -> TrackWithMotionModel
         // (mTcw = mVelocity * mLastFrame.mTcw, :1519) unless the map holds fewer
         // than 4 keyframes (:602); else TrackPreviousFrame (mTcw = mLastFrame.mTcw,
@@ -173,7 +173,9 @@ __global__ __launch_bounds__(256) void k_fe_begin(FeDev D) {
         const int kfc = D.kfc[b];
         // a parked stream (NOT_INITIALIZED) takes no path: no search, no relocalisation
         const int state = T[GF_TR_STATE];
-        const int path = state == 2 ? 4 : state == 1 ? 3 : (T[GF_TR_VEL] && since >= 2 && !(kfc >= 0 && kfc < 4)) ? 0 : 2;
+        // a pending ForceRelocalisation takes the relocalisation branch from WORKING too (:584, :622)
+        const bool reloc = state == 1 || T[GF_TR_FORCE] != 0;
+        const int path = state == 2 ? 4 : reloc ? 3 : (T[GF_TR_VEL] && since >= 2 && !(kfc >= 0 && kfc < 4)) ? 0 : 2;
         T[GF_TR_PATH] = path;
         T[GF_TR_OK] = 0;
         D.m3_nlast[b] = path == 0 ? D.last_nkp[b] : 0;
@@ -955,6 +957,12 @@ struct gf_frontend {
     // map compaction (gf_frontend_compact_maps): the staged requests, the remap
     // tables and the device's verdict per listed stream, allocated on first use
     int32_t *mc_stage = nullptr, *mc_mp_remap = nullptr, *mc_kf_remap = nullptr, *mc_res = nullptr;
+    // forced relocalisation (gf_frontend_force_relocalisation): [B][2] requests, device staging and two pinned
+    // buffers used in turn, each guarded by the event of the upload that last read it
+    int32_t* fr_stage = nullptr;
+    int32_t* fr_pin[2] = {nullptr, nullptr};
+    hipEvent_t fr_ev[2] = {nullptr, nullptr};
+    int fr_turn = 0;
 };
 
 namespace {
@@ -1001,6 +1009,10 @@ void fe_free(gf_frontend* fe) {
         if (fe->mu_ev[i]) (void)hipEventDestroy(fe->mu_ev[i]);
         fe->mu_pin[i] = nullptr;
         fe->mu_ev[i] = nullptr;
+        if (fe->fr_pin[i]) (void)hipHostFree(fe->fr_pin[i]);
+        if (fe->fr_ev[i]) (void)hipEventDestroy(fe->fr_ev[i]);
+        fe->fr_pin[i] = nullptr;
+        fe->fr_ev[i] = nullptr;
     }
     for (void* p : fe->kg_old_pins) (void)hipHostFree(p);
     fe->kg_old_pins.clear();
@@ -2632,6 +2644,8 @@ int fe_apply_deltas(gf_frontend* fe, int ndelta, const gf_map_delta* deltas, con
 
 }  // namespace
 
+static int fr_alloc(gf_frontend* fe);
+
 // ------------------------------------------------------------ park and reset
 int gf_frontend_set_lifecycle(gf_frontend* fe, int on) {
     GF_CHECK(fe, GF_ERR_ARG, "null front end");
@@ -2648,6 +2662,7 @@ int gf_frontend_set_lifecycle(gf_frontend* fe, int on) {
     // this front end never allocates or synchronises, the first one after a capture included
     FE_RC(mu_alloc(fe));
     FE_RC(ss_alloc(fe));
+    FE_RC(fr_alloc(fe));
     const gf_covis_map empty{};
     const int32_t parked = 2;
     for (int b = 0; b < fe->D.B; b++) {
@@ -2663,6 +2678,77 @@ int gf_frontend_lifecycle_read(gf_frontend* fe, int32_t* state) {
     GF_HIP(hipSetDevice(fe->ctx->device));
     GF_HIP(hipStreamSynchronize(fe->ctx->stream));
     GF_HIP(hipMemcpy2D(state, 4, fe->D.track + GF_TR_STATE, 4 * GF_TR_N, 4, (size_t)fe->D.B, hipMemcpyDeviceToHost));
+    return GF_OK;
+}
+
+// ------------------------------------------------------ forced relocalisation
+// Staging on first use: B requests of two words.
+static int fr_alloc(gf_frontend* fe) {
+    if (fe->fr_stage) return GF_OK;
+    const size_t bytes = 8 * (size_t)fe->D.B;
+    for (int i = 0; i < 2; i++) {  // a call that failed half-way left what it had allocated
+        if (!fe->fr_pin[i]) GF_HIP(hipHostMalloc((void**)&fe->fr_pin[i], bytes, hipHostMallocDefault));
+        if (!fe->fr_ev[i]) GF_HIP(hipEventCreateWithFlags(&fe->fr_ev[i], hipEventDisableTiming));
+    }
+    void* p = nullptr;
+    FE_RC(fe_alloc(fe, bytes, &p));
+    GF_HIP(hipDeviceSynchronize());  // fe_alloc clears on the null stream: before the first upload
+    fe->fr_stage = (int32_t*)p;      // last: marks the staging as complete
+    return GF_OK;
+}
+
+int gf_frontend_force_relocalisation(gf_frontend* fe, int n, const int32_t* streams, const int32_t* last_kf) {
+    GF_CHECK(fe && n >= 0 && (n == 0 || streams), GF_ERR_ARG, "bad arguments");
+    if (n == 0) return GF_OK;
+    GF_CHECK(!fe->extracted, GF_ERR_ARG, "the extracted frame has not been tracked (gf_frontend_step_track)");
+    const int B = fe->D.B;
+    GF_CHECK(n <= B, GF_ERR_ARG, "a stream is named at most once");
+    // everything is decided before anything is written
+    std::vector<uint8_t> named(B, 0);
+    for (int i = 0; i < n; i++) {
+        const int b = streams[i];
+        GF_CHECK(b >= 0 && b < B, GF_ERR_ARG, "bad stream");
+        const std::string at = "stream " + std::to_string(b) + ": ";
+        GF_CHECK(!named[b], GF_ERR_ARG, at + "named twice");
+        named[b] = 1;
+        GF_CHECK(fe->covis_set && fe->has_covis[b] && fe->h_kfc[b] > 0, GF_ERR_ARG,
+                 at + "a forced relocalisation needs a keyframe graph with a keyframe (gf_frontend_set_covis)");
+        GF_CHECK(fe->voc, GF_ERR_ARG, at + "a forced relocalisation needs a vocabulary (gf_frontend_set_vocab)");
+        GF_CHECK(fe->rl_alloc && (fe->h_kfdb[b].nkf > 0 || fe->kfdb_obj[b]), GF_ERR_ARG,
+                 at + "a forced relocalisation needs the stream's keyframe database (gf_frontend_set_kfdb)");
+        const int kf = last_kf ? last_kf[i] : -1;
+        GF_CHECK(kf >= -1 && kf < fe->h_kfc[b], GF_ERR_ARG, at + "last_kf is not a keyframe of the stream's graph");
+    }
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    hipStream_t s = fe->ctx->stream;
+    FE_RC(fr_alloc(fe));
+    const int turn = fe->fr_turn;
+    GF_HIP(hipEventSynchronize(fe->fr_ev[turn]));  // the upload that last read this buffer (two calls ago)
+    int32_t* pin = fe->fr_pin[turn];
+    for (int i = 0; i < n; i++) {
+        pin[2 * i] = streams[i];
+        pin[2 * i + 1] = last_kf ? last_kf[i] : -1;
+    }
+    GF_HIP(hipMemcpyAsync(fe->fr_stage, pin, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+    GF_HIP(hipEventRecord(fe->fr_ev[turn], s));
+    fe->fr_turn = turn ^ 1;
+    gf::ForceRelocArgs A{};
+    A.stage = fe->fr_stage;
+    A.n = n;
+    A.B = B;
+    A.track = fe->D.track;
+    A.covis = fe->d_covis;
+    return gf::force_reloc_launch(fe->ctx, A, s);
+}
+
+int gf_frontend_reloc_candidates_read(gf_frontend* fe, int32_t* cands, int32_t* ncand) {
+    GF_CHECK(fe && cands && ncand, GF_ERR_ARG, "null arg");
+    GF_CHECK(fe->rl_alloc, GF_ERR_ARG, "no relocalisation buffers (gf_frontend_set_kfdb)");
+    GF_HIP(hipSetDevice(fe->ctx->device));
+    GF_HIP(hipStreamSynchronize(fe->ctx->stream));
+    const size_t B = fe->D.B;
+    GF_HIP(hipMemcpy(cands, fe->TL.cands, 4 * B * gf::RL_NC, hipMemcpyDeviceToHost));
+    GF_HIP(hipMemcpy(ncand, fe->TL.ncand, 4 * B, hipMemcpyDeviceToHost));
     return GF_OK;
 }
 
@@ -2807,6 +2893,7 @@ int gf_frontend_compact_maps(gf_frontend* fe, int nreq, const gf_map_compact* re
     A.left = D.left;
     A.nleft = D.stats + (size_t)GF_ST_NLEFT * B;
     A.ref_kf = fe->ref_kf;
+    A.track = D.track;
     if (fe->kf_alloc) {
         A.kf_state = fe->KA.state;
         A.out_hdr = fe->KA.out_hdr;

@@ -53,6 +53,7 @@ struct MapCompactArgs {
     int32_t* left;
     const int32_t* nleft;
     int32_t* ref_kf;
+    int32_t* track;             // [B][GF_TR_N]: GF_TR_FORCE_KF of a pending forced relocalisation
     int32_t* kf_state;          // [B][GF_KF_N] or null: no keyframe stage
     const gf_keyframe_hdr* out_hdr;
     int32_t* out_slots;         // [B][cap]

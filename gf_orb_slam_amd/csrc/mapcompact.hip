@@ -101,6 +101,10 @@ __global__ __launch_bounds__(256) void k_mc_mark(MapCompactArgs A) {
     if (t == 0) {
         const int r = A.ref_kf[b];
         if (r >= 0 && r < nk) kk[r] = 1;
+        // mpLastKeyFrame of a pending ForceRelocalisation: the next step's candidate list starts from it
+        const int32_t* T = A.track + (size_t)b * GF_TR_N;
+        const int f = T[GF_TR_FORCE_KF];
+        if (T[GF_TR_FORCE] && f >= 0 && f < nk) kk[f] = 1;
     }
 }
 
@@ -334,6 +338,8 @@ __device__ void renumber_holders(const MapCompactArgs& A, const McHdr* H, const 
     if (kf_pending(A, b)) renumber(A.out_slots + ko, clampi(A.out_hdr[b].n, 0, A.cap), km, n);
     if (threadIdx.x == 0) {
         A.ref_kf[b] = renum(A.ref_kf[b], kk, nk);
+        int32_t* T = A.track + (size_t)b * GF_TR_N;
+        if (T[GF_TR_FORCE]) T[GF_TR_FORCE_KF] = renum(T[GF_TR_FORCE_KF], kk, nk);  // pinned: never -1
         if (A.kf_state) {
             int32_t* S = A.kf_state + (size_t)b * GF_KF_N;
             S[GF_KF_REF] = renum(S[GF_KF_REF], kk, nk);

@@ -809,7 +809,30 @@ __global__ __launch_bounds__(TL_T) void k_reloc_cand(gf::TrackLossArgs A) {
     const int b = blockIdx.x, lane = threadIdx.x, cap = A.cap;
     const gf::KfdbDev& db = A.kfdb[b];
     int nc = 0;
-    if (A.rl_gate[b] && db.nkf > 0) {
+    int32_t* T = A.track + (size_t)b * GF_TR_N;
+    // ForceRelocalisation (Tracking.cc:3864-3879): the flag is cleared first, and the candidates are the local
+    // window around the last keyframe, GetBestCovisibilityKeyFrames(9) then the keyframe itself; the database
+    // is not asked and the keyframes' query state stays. A parked stream (no gate) keeps its request.
+    const bool forced = A.rl_gate[b] && T[GF_TR_FORCE] != 0;
+    if (forced) {
+        const gf_covis_map& cv = A.covis[b];
+        const int kf = T[GF_TR_FORCE_KF];
+        int32_t* cands = A.cands + (size_t)b * gf::RL_NC;
+        if (kf >= 0 && kf < cv.nkf) {  // the host checked the range; compaction renumbers it
+            const int o = cv.kf_cov_off[kf];
+            // (the pair slots hold the largest database's keyframes: a graph of distinct keyframes fits)
+            const int nn = min(min(9, A.ncs - 1), cv.kf_cov_off[kf + 1] - o);
+            if (lane < nn) cands[lane] = cv.kf_cov[o + lane];
+            if (lane == 0) cands[nn] = kf;
+            nc = nn + 1;
+        }
+        __syncthreads();  // every lane has read the words; the list is visible to the pair loop below
+        if (lane == 0) {
+            T[GF_TR_FORCE] = 0;
+            T[GF_TR_FORCE_KF] = 0;
+            stat_of(A, GF_ST_FLAGS)[b] |= 65536;
+        }
+    } else if (A.rl_gate[b] && db.nkf > 0) {
         const gf_covis_map& cv = A.covis[b];
         nc = reloc_candidates_wave(db, cv.kf_bad, cv.kf_cov_off, cv.kf_cov, A.words + (size_t)b * cap,
                                    A.values + (size_t)b * cap, A.nwords[b],
@@ -825,8 +848,9 @@ __global__ __launch_bounds__(TL_T) void k_reloc_cand(gf::TrackLossArgs A) {
     for (int i = lane; i < A.ncs; i += TL_T) {
         gf::BowPairDev p{};
         p.out = A.bow_out + ((size_t)b * A.ncs + i) * cap;
-        if (i < nc) {
-            const int kf = A.cands[(size_t)b * gf::RL_NC + i];
+        // a forced candidate the database does not hold keeps the empty pair: no matches, discarded
+        const int kf = i < nc ? A.cands[(size_t)b * gf::RL_NC + i] : -1;
+        if (kf >= 0 && kf < db.nkf) {
             p.a.fv_nodes = db.fv_nodes + db.fv_off[kf];
             p.a.fv_start = db.fv_start + db.fv_off[kf];
             p.a.fv_feats = db.fv_feats;

@@ -63,4 +63,14 @@ struct StreamStartArgs {
 
 int stream_start_launch(gf_ctx* ctx, const StreamStartArgs& a, hipStream_t s);
 
+// gf_frontend_force_relocalisation: the staged requests are (stream, last_kf)
+// pairs, last_kf -1 for the newest keyframe that is not bad.
+struct ForceRelocArgs {
+    const int32_t* stage;  // [n][2]
+    int n, B;
+    int32_t* track;              // [B][GF_TR_N]
+    const gf_covis_map* covis;   // [B]
+};
+int force_reloc_launch(gf_ctx* ctx, const ForceRelocArgs& a, hipStream_t s);
+
 }  // namespace gf

@@ -14,6 +14,8 @@
 //                 every "before" count from their header, which the host packed
 //                 from mirrors it had emptied, and that is what makes the delta
 //                 the whole map
+//   k_force_reloc the request of gf_frontend_force_relocalisation: the three
+//                 tracking words of each named stream, one thread a request
 // Every destination has one writer: a row chunk belongs to one workgroup and
 // the words of a stream to chunk 0. Nothing waits on another workgroup; a
 // stream not named is not touched and costs nothing. The kernel runs on the
@@ -102,6 +104,8 @@ __global__ __launch_bounds__(SS_ROWS) void k_ss_install(StreamStartArgs A) {
     T[GF_TR_PATH] = 2;
     T[GF_TR_QUERY] = H->frame_id;
     T[GF_TR_OK] = 1;
+    T[GF_TR_FORCE] = 0;  // a pending ForceRelocalisation belonged to the old map
+    T[GF_TR_FORCE_KF] = 0;
     if (A.kf_state) {
         int32_t* S = A.kf_state + (long long)b * GF_KF_N;
         S[GF_KF_SINCE] = 0;    // mnLastKeyFrameId = mCurrentFrame.mnId (:1309)
@@ -128,9 +132,44 @@ __global__ __launch_bounds__(SS_ROWS) void k_ss_install(StreamStartArgs A) {
     }
 }
 
+// Tracking::ForceRelocalisation (Tracking.cc:4035-4045) for the streams a call
+// names: one thread per request. last_kf -1 is the newest keyframe of the graph
+// that is not bad (the newest one when all are). The host has checked the
+// streams (distinct, in range, a graph with keyframes) and last_kf's range.
+__global__ __launch_bounds__(64) void k_force_reloc(gf::ForceRelocArgs A) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= A.n) return;
+    const int b = A.stage[2 * i];
+    int kf = A.stage[2 * i + 1];
+    if (b < 0 || b >= A.B) return;
+    const int nkf = A.covis[b].nkf;
+    if (kf < 0) {
+        const uint8_t* bad = A.covis[b].kf_bad;
+        kf = nkf - 1;
+        for (int k = nkf - 1; k >= 0; k--)
+            if (!bad[k]) {
+                kf = k;
+                break;
+            }
+    }
+    if (kf < 0 || kf >= nkf) return;  // not reached: the mirrors the host checked against follow the device
+    int32_t* T = A.track + (long long)b * GF_TR_N;
+    T[GF_TR_FORCE] = 1;
+    T[GF_TR_FORCE_KF] = kf;
+    T[GF_TR_SINCE] = 0;  // mnLastRelocFrameId = mCurrentFrame.mnId (:4044)
+}
+
 }  // namespace
 
 namespace gf {
+
+int force_reloc_launch(gf_ctx* ctx, const ForceRelocArgs& a, hipStream_t s) {
+    if (a.n <= 0) return GF_OK;
+    GF_PROF(ctx, s, "k_force_reloc");
+    GF_LAUNCH(k_force_reloc, (a.n + 63) / 64, 64, 0, s, a);
+    GF_HIP(hipGetLastError());
+    return GF_OK;
+}
 
 int stream_start_launch(gf_ctx* ctx, const StreamStartArgs& a, hipStream_t s) {
     GF_PROF(ctx, s, "k_ss_install");

@@ -74,7 +74,7 @@ STATS = ["m3", "found", "to_match", "branch", "in_view", "local", "inl1", "inl2"
          "iter2", "edges1", "edges2", "flags", "frames", "ldets", "nlocal", "ncut", "cand_last", "cand_proj",
          "tpf", "ncand", "reloc", "ransac"]
 # GF_FE_TRACK columns and path codes
-TR = {"state": 0, "vel": 1, "since": 2, "path": 3, "query": 4, "ok": 5}
+TR = {"state": 0, "vel": 1, "since": 2, "path": 3, "query": 4, "ok": 5, "force": 6, "force_kf": 7}
 PATHS = {0: "motion model", 1: "previous frame after the motion model", 2: "previous frame", 3: "relocalisation",
          4: "none (parked)"}
 STATES = {0: "WORKING", 1: "LOST", 2: "NOT_INITIALIZED"}  # GF_TR_STATE; 2: the stream is parked
@@ -451,6 +451,36 @@ class FrontEnd:
                 db.clear()
                 if r.kf_rows is not None:
                     db.extend(r.kf_rows)
+
+    def force_relocalisation(self, streams, last_kf=None) -> None:
+        """gf_frontend_force_relocalisation (Tracking::ForceRelocalisation,
+        Tracking.cc:4035-4045): the next step of each stream in ``streams``
+        (an index or a list, each at most once) relocalises although the
+        stream is WORKING, against the local window around ``last_kf`` (graph
+        keyframe indices, one per stream; None or -1: the stream's newest
+        keyframe that is not bad): the first 9 entries of its covisibility row,
+        then the keyframe. Behind the last step, without a host
+        synchronisation; legal after capture_graph(). A refused request
+        (GFError) writes nothing."""
+        ss = np.atleast_1d(np.asarray(streams, np.int32)).copy()
+        if not len(ss):
+            return
+        kf = None
+        if last_kf is not None:
+            kf = np.atleast_1d(np.asarray(last_kf, np.int32)).copy()
+            if len(kf) != len(ss):
+                raise ValueError("one last_kf per stream")
+        check(lib().gf_frontend_force_relocalisation(self.handle, len(ss), ptr(ss), ptr(kf) if kf is not None else None))
+
+    def reloc_candidates(self) -> list:
+        """gf_frontend_reloc_candidates_read: per stream, the relocalisation
+        candidates (graph keyframe indices, in the order they were tried) of
+        the last step; empty for a stream that did not relocalise.
+        Synchronises."""
+        c = np.zeros((self.B, 64), np.int32)
+        n = np.zeros(self.B, np.int32)
+        check(lib().gf_frontend_reloc_candidates_read(self.handle, ptr(c), ptr(n)))
+        return [c[b, :max(int(n[b]), 0)].copy() for b in range(self.B)]
 
     def covis(self, stream: int) -> dict:
         """gf_frontend_get_covis: the keyframe graph the front end holds for

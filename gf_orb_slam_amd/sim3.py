@@ -601,7 +601,9 @@ def correct_loop(map, cur_kf, matched_kf, gScw, current_matched_points, loop_poi
     :func:`search_and_fuse`; the LoopConnections loop;
     ``Optimizer.OptimizeEssentialGraph`` with its write-back and
     UpdateNormalAndDepth; the mutual loop edge. RequestStop,
-    ForceRelocalisation, SetFlagAfterBA and mLastLoopKFid are the caller's.
+    ForceRelocalisation, SetFlagAfterBA and mLastLoopKFid are the caller's
+    (``tracking.KeyFrameInserter.correct_loop`` does the first two for a
+    tracked stream).
     -> the essential-graph result dict plus ``LoopConnections``, ``fuse`` (the
     report of search_and_fuse), ``CorrectedSim3`` and ``NonCorrectedSim3``."""
     from .optimizer import Optimizer

@@ -998,3 +998,51 @@ class KeyFrameInserter:
         """LocalMapping::Release (:138-141)."""
         self.stop_requested[stream] = False
         self.fe.set_keyframe_state(stream, stop=0)
+
+    def loop_corrected(self, stream: int, last_kf=None) -> int:
+        """The arrow from the loop closer to the tracker
+        (``mpTracker->ForceRelocalisation()``, LoopClosing.cc:554): the
+        stream's corrected map goes to the front end (``feed_back([stream])``:
+        every moved, replaced and bad point, the slot writes, the changed
+        observation rows and covisibility lists), then
+        ``FrontEnd.force_relocalisation`` makes the stream's next step
+        relocalise against the local window around ``last_kf``, a keyframe id
+        of the stream's ``LoopMap`` (mpLastKeyFrame; default: the highest id
+        the front end holds that is not bad), translated through the
+        feedback's ``kf_index``. A refused update (GFError) sends no request.
+        -> the graph keyframe index sent."""
+        stream = int(stream)
+        fb = self.feedback[stream]
+        self.feed_back([stream])
+        m = fb.map
+        if last_kf is None:
+            held = [int(k) for k in fb.kf_id if not m.kf_bad[int(k)]]
+            if not held:
+                raise ValueError(f"stream {stream}: the front end holds no good keyframe of the map")
+            last_kf = max(held)
+        last_kf = int(last_kf)
+        if not 0 <= last_kf < len(fb.kf_index) or fb.kf_index[last_kf] < 0:
+            raise ValueError(f"stream {stream}: the front end does not hold keyframe {last_kf}")
+        idx = int(fb.kf_index[last_kf])
+        self.fe.force_relocalisation([stream], [idx])
+        return idx
+
+    def correct_loop(self, stream: int, cur_kf, matched_kf, gScw, current_matched_points, loop_points, last_kf=None,
+                     ctx=None) -> dict:
+        """LoopClosing::CorrectLoop (LoopClosing.cc:426-560) for a tracked
+        stream: ``request_stop`` (:430), ``sim3.correct_loop`` on the stream's
+        mapper's map, :meth:`loop_corrected`, ``release`` (:559). The reference
+        raises the flag before OptimizeEssentialGraph while its tracker runs on
+        a thread of its own; here the whole correction is applied before the
+        next step sees any of it. -> ``sim3.correct_loop``'s report."""
+        from . import sim3
+
+        stream = int(stream)
+        self.request_stop(stream)
+        try:
+            rep = sim3.correct_loop(self.mappers[stream].map, cur_kf, matched_kf, gScw, current_matched_points,
+                                    loop_points, ctx)
+            self.loop_corrected(stream, last_kf)
+        finally:
+            self.release(stream)
+        return rep

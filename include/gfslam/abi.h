@@ -1850,6 +1850,10 @@ enum {
                            3 Relocalisation, 4 none (the stream is parked)   */
     GF_TR_QUERY,        /* mnId of the last frame (the keyframe database's query id) */
     GF_TR_OK,           /* bOK of the last step's initial estimate           */
+    GF_TR_FORCE,        /* mbForceRelocalisation: 1 while a request of
+                           gf_frontend_force_relocalisation is pending, else 0 */
+    GF_TR_FORCE_KF,     /* mpLastKeyFrame of a pending request (graph keyframe
+                           index), else 0                                     */
     GF_TR_N = 8
 };
 /* KeyFrame::mnRelocQuery / mnRelocWords / mRelocScore of one keyframe of a
@@ -1882,7 +1886,9 @@ enum {
                            SearchAdditionalMatchesInFrame, 1024: SearchByProjection_Budget cap,
                            2048: TrackPreviousFrame ran, 4096: Relocalisation ran,
                            8192: the initial estimate failed (no TrackLocalMap),
-                           16384: TrackLocalMap failed, 32768: relocalised */
+                           16384: TrackLocalMap failed, 32768: relocalised,
+                           65536: the relocalisation of this step was a forced
+                           one (gf_frontend_force_relocalisation)            */
     GF_ST_FRAMES,       /* frames tracked                                   */
     GF_ST_LDETS,        /* logDet evaluations of runActiveMapMatching (heap
                            pushes, Observability.cc:1373): SURVEY §8d E_ld  */
@@ -2261,6 +2267,44 @@ typedef struct gf_stream_start {
  * byte-identical before and after; n == 0 launches nothing. */
 int gf_frontend_start_streams(gf_frontend* fe, int n, const gf_stream_start* reqs,
                               const gf_keyframe_db* const* kf_rows);
+/* ------------------------------------------------------ ForceRelocalisation
+ * Tracking::ForceRelocalisation (Tracking.cc:4035-4045), what
+ * LoopClosing::CorrectLoop calls after it has moved the map (LoopClosing.cc:
+ * 554): the next step of each named stream takes the relocalisation branch
+ * although the stream is WORKING (Tracking.cc:584, 622-628), and Relocalisation
+ * does not ask the keyframe database: its candidates are the local window
+ * around the last keyframe, mpLastKeyFrame->GetBestCovisibilityKeyFrames(9)
+ * followed by mpLastKeyFrame (:3866-3879).
+ * The request writes, per named stream, GF_TR_FORCE = 1, GF_TR_FORCE_KF =
+ * last_kf[i] and GF_TR_SINCE = 0 (:4044, mnLastRelocFrameId = mCurrentFrame.
+ * mnId): one upload and one small kernel on the context's stream behind the
+ * last step, with no host synchronisation (the first call allocates its
+ * staging and synchronises once); legal after gf_frontend_capture. last_kf
+ * NULL or last_kf[i] == -1: the newest keyframe of the stream's graph that is
+ * not bad (the device reads kf_bad; the newest one when all are bad).
+ * The next step of such a stream: GF_TR_PATH 3 whatever GF_TR_STATE is, except
+ * that a parked stream (state 2) stays on path 4 and keeps the request pending,
+ * byte for byte. The candidate list is the first min(9, row length) entries of
+ * FORCE_KF's covisibility row in the row's order, then FORCE_KF; GF_ST_NCAND is
+ * its length, GF_ST_FLAGS gains 65536, both words go back to 0 before the list
+ * is used (the reference clears the flag first, :3864: a forced relocalisation
+ * that fails leaves a LOST stream that asks the database from the next frame
+ * on), and the keyframes' query state (GF_FE_RELOC) is not touched. A candidate
+ * the stream's database does not hold (index >= its keyframe count) has no
+ * SearchByBoW matches and is discarded by nmatches < 15; bad keyframes are
+ * discarded as in every relocalisation. gf_frontend_start_streams clears a
+ * pending request; map compaction pins and renumbers FORCE_KF as it does the
+ * reference keyframe.
+ * Decided on the host, nothing written: GF_ERR_ARG for a stream out of range or
+ * named twice, a stream without a keyframe graph (an empty one included) and
+ * last_kf outside [-1, keyframes of the graph); without a vocabulary or without
+ * a database on the stream, the status the step's relocalisation is refused
+ * with (GF_ERR_ARG). n == 0 launches nothing. */
+int gf_frontend_force_relocalisation(gf_frontend* fe, int n, const int32_t* streams, const int32_t* last_kf);
+/* The relocalisation candidates every stream used in the last step: cands
+ * [B][64] (entries past ncand[b] are whatever an earlier step left) and
+ * ncand[B]; 0 for a stream that did not relocalise. Synchronises. */
+int gf_frontend_reloc_candidates_read(gf_frontend* fe, int32_t* cands, int32_t* ncand);
 /* The keyframe graph the front end holds for a stream. counts[5] = nkf, nmp,
  * slots, covisibility entries, observations (always written); the arrays of
  * `out` are caller buffers with caps[3] = slot, covisibility and observation
@@ -2300,8 +2344,9 @@ int gf_frontend_get_covis(gf_frontend* fe, int stream, int32_t* counts, const gf
  * past the new counts keep whatever bytes they held.
  * Pins: a point the next step can still read through frame state is kept even
  * when listed: the points of GF_FE_KP2MP[0..nkp), GF_FE_LAST_KP2MP[0..last_nkp)
- * and the slots of a pending outbox keyframe (GF_KF_PENDING); so is the
- * keyframe the persistent reference-keyframe word names. The device decides
+ * and the slots of a pending outbox keyframe (GF_KF_PENDING); so are the
+ * keyframe the persistent reference-keyframe word names and the GF_TR_FORCE_KF
+ * of a pending forced relocalisation. The device decides
  * (a mark pass before the scan) and reports: n_kept_* count the listed items
  * that stayed, and the remap tables say where everything went. A pinned point
  * whose keyframes are all gone keeps an empty observation row. Those holders

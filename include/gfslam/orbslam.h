@@ -436,6 +436,18 @@ inline std::vector<eTrackingState> TrackingStates(gf_frontend* pFrontEnd, int nS
     return out;
 }
 
+/* ------------------------------------------------- Tracking::ForceRelocalisation */
+/* What LoopClosing::CorrectLoop calls on the tracker (LoopClosing.cc:554,
+ * Tracking.cc:4035-4045), for one stream of a batched front end, after the
+ * corrected map has been sent with gf_frontend_update_maps: the stream's next
+ * step relocalises against the local window around its last keyframe
+ * (Tracking.cc:3866-3879). nLastKeyFrame is mpLastKeyFrame as an index of the
+ * stream's keyframe graph; -1: the newest keyframe that is not bad. */
+inline void ForceRelocalisation(gf_frontend* pFrontEnd, int nStream, int nLastKeyFrame = -1) {
+    const int32_t stream = nStream, kf = nLastKeyFrame;
+    if (gf_frontend_force_relocalisation(pFrontEnd, 1, &stream, &kf) != GF_OK) throw std::runtime_error(gf_last_error());
+}
+
 }  // namespace ORB_SLAM
 
 #endif /* GFSLAM_ORBSLAM_H */
