@@ -390,10 +390,16 @@ class LocalBAPlan:
         check(lib().gf_ba_plan_results_dev(self.handle, int(p), ctypes.byref(T), ctypes.byref(X), ctypes.byref(I)))
         return T.value, X.value, I.value
 
-    def solve(self, stream=None) -> int:
+    def solve(self, stream=None, stop_flag=None) -> int:
+        """gf_ba_plan_solve_stop (gf_ba_plan_solve is the same call with a null
+        flag). stop_flag: optional ctypes.c_uint8 standing for mbAbortBA. The
+        host reads it through its address before every chunk of steps, so the
+        caller keeps the object alive until solve() returns; another thread
+        may set it meanwhile. Returns the steps enqueued."""
         steps = ctypes.c_int()
-        check(lib().gf_ba_plan_solve(self.handle, stream if stream is not None else self.ctx.stream,
-                                     ctypes.byref(steps)))
+        check(lib().gf_ba_plan_solve_stop(self.handle, stream if stream is not None else self.ctx.stream,
+                                          ctypes.byref(stop_flag) if stop_flag is not None else None,
+                                          ctypes.byref(steps)))
         return steps.value
 
     def results(self) -> list:
